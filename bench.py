@@ -34,6 +34,30 @@ from benchlib.measure import (BOX_ATTN_EXPONENT, BOX_ATTN_REFERENCE_MS, BOX_CALI
                               MFMA_PEAK_TFLOPS_BF16, attn_pmc_fields, box_calib_tflops, flf_gate_ms, synthetic_inputs, tracked_body_ms)
 
 
+def window_start(K, Wm, guide=15):
+    """First schedule step of the warm-up + timed window: n_g = max(1, round(0.3 K)) of the K timed steps are guided (< guide)."""
+    n_g = min(max(1, round(0.3 * K)) if K > 1 else 1, K)
+    return max(0, guide - Wm - n_g)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy in float32.  If they exceed DUMP_LIMIT_BYTES together, each is replaced by a fixed
+    seeded sample of its flattened elements (the same indices on every run), so that two builds stay comparable element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in host.values())
+    for name, v in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            n = max(1, v.size * DUMP_LIMIT_BYTES // total)
+            idx = np.sort(np.random.default_rng(0).choice(v.size, size=n, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     ap = argparse.ArgumentParser()
@@ -82,7 +106,17 @@ def main(argv=None):
                          "1-GPU run appends to the line as `also`")
     ap.add_argument("--workload", default="wan", choices=["wan", "longcat"],
                     help="wan = the BASELINE metric (default); longcat = the same contract on LongCat-Video 13.6B guided i2v (config 4's model)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed window, write what the timed path returned (the latents after its last step) as DIR/<name>.npy "
+                         "in float32; the inputs are seeded, so two builds run with the same arguments can be compared output for output")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.workload != "wan":
+        raise SystemExit("bench.py: --dump-outputs is implemented for --workload wan only")
+    if a.workload == "wan" and window_start(a.steps, a.warmup) + a.warmup + a.steps > 50:
+        # the window would run past the end of the schedule: fewer than --steps steps would be timed
+        raise SystemExit(f"bench.py: --warmup + --steps ({a.warmup} + {a.steps}) must fit the 50-step schedule")
     if a.vae_precision is None:
         a.vae_precision = "bf16" if a.workload == "longcat" else "fp16x3"
     a.vae_precision = {"fp32": "fp16x3", "tf32": "fp16"}.get(a.vae_precision, a.vae_precision)
@@ -164,10 +198,8 @@ def main(argv=None):
             exchange.update(selected=names[0], selection="default (simulated rank: the calibration shows each mode's compute cost only)")
         del xcal
     K, Wm = a.steps, a.warmup
-    n_g = max(1, round(0.3 * K)) if K > 1 else 1
-    n_g = min(n_g, K)
     guide = 15
-    start = max(0, guide - Wm - n_g)
+    start = window_start(K, Wm, guide)
     marks = {}
 
     def barrier():
@@ -202,11 +234,14 @@ def main(argv=None):
             marks["calib1"] = box_calib_tflops(device)
 
     gen = torch.manual_seed(42)
-    pipe(image=image, height=a.height, width=a.width, num_frames=a.frames, num_inference_steps=50, guidance_scale=4.0,
-         generator=gen, prompt_embeds=text, negative_prompt_embeds=neg, image_embeds=img_emb, output_type="latent",
-         video_ref=ref, mask=mask, guided=True, resample_steps=2, guide_steps=guide, omega=4.0, omega_resample=4.0,
-         resample_round=guide, use_pca_channel_selection=True, static=True, start_step=start, max_steps=Wm + K, step_hook=hook)
+    result = pipe(image=image, height=a.height, width=a.width, num_frames=a.frames, num_inference_steps=50, guidance_scale=4.0,
+                  generator=gen, prompt_embeds=text, negative_prompt_embeds=neg, image_embeds=img_emb, output_type="latent",
+                  video_ref=ref, mask=mask, guided=True, resample_steps=2, guide_steps=guide, omega=4.0, omega_resample=4.0,
+                  resample_round=guide, use_pca_channel_selection=True, static=True, start_step=start, max_steps=Wm + K, step_hook=hook)
     elapsed = marks["t1"] - marks["t0"]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"latents": result.frames})
+    del result
     el = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if comm is not None:
         comm.all_reduce_max(el)

@@ -313,3 +313,51 @@ def test_exchange_calibration_picks_by_extrapolated_time_and_keeps_the_default_o
     # forced
     out3 = bench.calibrate_exchange(model, world, run, ["lockstep"], "num_layers", torch.device("cpu"), "cfg2+gather", ctx=ctx)
     assert out3["selected"] == "cfg2+gather" and model.comm is sub and model.exchange_mode == "gather"
+
+
+def test_dump_outputs_writes_float32_and_samples_the_same_elements_over_the_limit(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: what the timed path returned, as DIR/<name>.npy in float32; over the size limit a fixed seeded sample
+    of each array, the same indices on every call, so that two builds can be compared element for element."""
+    import numpy as np
+    import torch
+
+    lat = torch.randn(1, 16, 3, 4, 5, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "a"), {"latents": lat})
+    got = np.load(tmp_path / "a" / "latents.npy")
+    assert got.dtype == np.float32 and got.shape == tuple(lat.shape)
+    np.testing.assert_array_equal(got, lat.float().numpy())
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1024)
+    big = torch.arange(4096, dtype=torch.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"x": big})
+    b, c = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert b.nbytes <= 1024 and b.size == 256
+    np.testing.assert_array_equal(b, c)
+    assert np.all(np.diff(b) > 0)                      # sampled values keep their order (here: the element indices themselves)
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--warmup", "-1"], ["--steps", "50"], ["--steps", "45", "--warmup", "6"],
+                                  ["--workload", "longcat", "--dump-outputs", "x"]])
+def test_bench_refuses_arguments_it_cannot_honour_before_any_gpu_call(argv, monkeypatch):
+    import torch
+
+    def boom(*a, **k):
+        raise AssertionError("touched the GPU")
+
+    monkeypatch.setattr(torch.cuda, "set_device", boom)
+    with pytest.raises(SystemExit) as e:
+        bench.main(argv)
+    assert e.value.code not in (0, None)
+
+
+def test_bench_window_times_exactly_steps_inside_the_schedule():
+    """--steps K --warmup W: K timed steps after W warm-up steps, max(1, round(0.3 K)) of them guided (schedule steps < 15)."""
+    for K in range(1, 50):
+        for Wm in range(0, 50 - K):
+            s = bench.window_start(K, Wm)
+            if s + Wm + K > 50:
+                continue
+            timed = range(s + Wm, s + Wm + K)
+            assert len(timed) == K and timed[-1] < 50
+            assert sum(i < 15 for i in timed) == min(K, max(1, round(0.3 * K))) or s == 0

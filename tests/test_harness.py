@@ -60,13 +60,15 @@ def test_prepare_inputs_takes_the_size_from_the_input_image(tmp_path):
     assert ref.shape == (1, 3, 2, h, w) and mask.shape == (1, 1, 2, h, w)
 
 
-def test_infer_negative_prompt_defaults_follow_static():
-    """INFER:277-285: the two negative prompts are literals of the entry point, picked by --static."""
+def test_infer_negative_prompt_defaults_follow_static(golden_dir):
+    """INFER:277-285: the two negative prompts are literals of the entry point, picked by --static (recorded from the reference entry
+    in tests/golden/infer_negative_prompts.json)."""
+    import json
+
     from worldforge_amd import infer
-    assert infer.NEGATIVE_PROMPT_STATIC.startswith("Blink, twinkle") and infer.NEGATIVE_PROMPT_DYNAMIC.startswith("Streaking objects")
-    if os.path.isdir("/root/reference/wan_for_worldforge"):
-        src = open("/root/reference/wan_for_worldforge/infer_worldforge.py").read()
-        assert infer.NEGATIVE_PROMPT_STATIC in src and infer.NEGATIVE_PROMPT_DYNAMIC in src
+    rec = json.load(open(os.path.join(golden_dir, "infer_negative_prompts.json")))
+    assert infer.NEGATIVE_PROMPT_STATIC == rec["negative_prompt_static"]
+    assert infer.NEGATIVE_PROMPT_DYNAMIC == rec["negative_prompt_dynamic"]
 
 
 def test_save_png_frames_round_trip(tmp_path):
