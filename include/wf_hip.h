@@ -172,6 +172,16 @@ int wf_gemm_f16(const void* X, const void* W, const float* bias, void* out, int 
  * (vae.py:252-258) of all frames in one launch. */
 int wf_gemm_f16_batched(const void* X, const void* W, void* out, int batch, int M, int N, int K, int ldx, int ldw, int ldo, int64_t bsx,
                         int64_t bsw, int64_t bso, int epilogue, void* stream);
+/* Opt-in MX-fp8 linear layers (csrc/mxfp8.hip; OCP MX: e4m3fn elements, one E8M0 scale 2^e per 32 consecutive K elements of a row).
+ * wf_mx_quant_e4m3: X bf16 [M, K] (row stride ldx % 8 == 0, 16-byte aligned) -> Q e4m3 [M, K] (8-byte aligned) + S E8M0 [M, K/32]; K % 32 == 0.
+ * e = the smallest integer with amax / 2^e <= 448, clamped to [-127, 127]; elements x / 2^e rounded to nearest even; an all-zero block
+ * gets scale byte 0; a block holding a NaN / Inf gets scale 0xff (E8M0 NaN) and NaN elements (0x7f). */
+int wf_mx_quant_e4m3(const void* X, void* Q, void* S, int M, int K, int ldx, void* stream);
+/* out[M,N] = epi(dequant(Xq, Xs) . dequant(Wq, Ws)^T + bias), fp32 accumulation; epilogue WF_EPI_BF16 / _BF16_GELU / _F32 / _RESID as
+ * wf_gemm_bf16.  Xq / Wq e4m3 with row strides ldx / ldw (bytes, % 16 == 0, 16-byte aligned), scales [rows, K/32] (4-byte aligned);
+ * K % 128 == 0, N % 4 == 0; anything else returns WF_EINVAL. */
+int wf_gemm_mxfp8(const void* Xq, const void* Xs, const void* Wq, const void* Ws, const float* bias, void* out, const float* gate, int M, int N,
+                  int K, int ldx, int ldw, int ldo, int epilogue, void* stream);
 
 /* flash_attention (attention.py:24-130) as used by model.py:149-154 (self) and :220-222 (cross): fused
  * softmax(Q K^T * softmax_scale) V, no mask, head_dim 128.  Q [H][Lq][128], K [H][Lkp][128] (rows >= kv_len zero),

@@ -31,6 +31,7 @@ SOURCES = {
     "inject.hip": ["-ffp-contract=off"],
     "flow.hip": ["-ffp-contract=off"],
     "gemm.hip": [],
+    "mxfp8.hip": [],
     "attention.hip": [],
     "dit_ops.hip": [],
     "longcat_ops.hip": ["-ffp-contract=off"],

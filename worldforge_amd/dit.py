@@ -55,9 +55,57 @@ def _pad64(n: int) -> int:
     return (n + 63) // 64 * 64
 
 
-def gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, epi: int,
+class MXWeight:
+    """The opt-in MX-fp8 form of a bf16 weight [N, K] (`linear_precision="mxfp8"`): e4m3 elements q [N, K] and E8M0 scales s [N, K/32]
+    of 32-element row blocks.  Row slices (the CFG prefix's qkv[:d] / qkv[d:]) slice both, so every row keeps its own scales."""
+
+    __slots__ = ("q", "s")
+
+    def __init__(self, q: torch.Tensor, s: torch.Tensor):
+        self.q, self.s = q, s
+
+    @classmethod
+    def quantize(cls, w: torch.Tensor) -> "MXWeight":
+        return cls(*ops.mx_quant(w))
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+    def __getitem__(self, rows: slice) -> "MXWeight":
+        assert isinstance(rows, slice)
+        return MXWeight(self.q[rows], self.s[rows])
+
+
+_MX_ACT = {}  # (device, stream) -> uint8 workspace of the quantized activation operand; stream order makes reuse safe
+
+
+def _mx_act(x: torch.Tensor):
+    M, K = x.shape
+    key = (x.device, ops.stream())
+    need = M * K + M * (K // 32)
+    buf = _MX_ACT.get(key)
+    if buf is None or buf.numel() < need:
+        buf = _MX_ACT[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
+    return ops.mx_quant(x, buf[:M * K].view(M, K), buf[M * K:need].view(M, K // 32))
+
+
+def quantize_linears(W: Dict[str, torch.Tensor], suffixes) -> Dict[str, object]:
+    """W with every matrix whose key ends in one of `suffixes` replaced by its MXWeight (the other entries are shared, not copied)."""
+    out = dict(W)
+    for k, v in W.items():
+        if k.endswith(tuple(suffixes)):
+            out[k] = MXWeight.quantize(v)
+    return out
+
+
+def gemm(x: torch.Tensor, w, bias: Optional[torch.Tensor], out: torch.Tensor, epi: int,
          gate: Optional[torch.Tensor] = None):
-    """out[M,N] = epi(x[M,K] @ w[N,K]^T + bias)."""
+    """out[M,N] = epi(x[M,K] @ w[N,K]^T + bias).  w: a bf16 matrix (wf_gemm_bf16), or an MXWeight -- then x is quantized to MX-fp8 in
+    front of the product (wf_mx_quant_e4m3 + wf_gemm_mxfp8)."""
+    if isinstance(w, MXWeight):
+        xq, xs = _mx_act(x)
+        return ops.gemm_mxfp8(xq, xs, w.q, w.s, bias, out, epi, gate)
     M, K = x.shape
     N = w.shape[0]
     assert w.shape[1] == K and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
@@ -311,7 +359,13 @@ def diffusers_key_map(num_layers: int) -> Dict[str, str]:
 class WanTransformer3DModel:
     dtype = torch.bfloat16
 
-    def __init__(self, cfg: DiTConfig, device="cuda:0", comm=None):
+    # the per-block token GEMMs that linear_precision="mxfp8" runs in MX-fp8 (embeddings, head and the prompt-context K / V stay bf16)
+    MX_LINEARS = ("qkv.w", "self_attn.o.w", "cross_attn.q.w", "cross_attn.o.w", "ffn.0.w", "ffn.2.w")
+
+    def __init__(self, cfg: DiTConfig, device="cuda:0", comm=None, linear_precision: str = "bf16"):
+        if linear_precision not in ("bf16", "mxfp8"):
+            raise ValueError(f"linear_precision must be 'bf16' or 'mxfp8', not {linear_precision!r}")
+        self.linear_precision = linear_precision
         self.cfg = cfg
         self.comm = comm  # parallel.Comm for sequence parallelism (None = single GPU)
         self.config = SimpleNamespace(patch_size=cfg.patch_size, in_channels=cfg.in_dim, out_channels=cfg.out_dim)
@@ -340,6 +394,8 @@ class WanTransformer3DModel:
         a monotonically increasing weights version, never by id() of a dict that may have been freed and its address reused."""
         self._wver = getattr(self, "_wver", 0) + 1
         self.__dict__.pop("_ctx_cache", None)
+        # mxfp8: the quantized copies are derived from the bf16 weights here, so an in-place edit never leaves a stale fp8 copy
+        self._wl = quantize_linears(self._w, self.MX_LINEARS) if self.linear_precision == "mxfp8" else self._w
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]):
         """Twin-keyed state dict (any dtype / device) -> device tensors: matrices bf16, vectors fp32, q/k/v fused."""
@@ -408,7 +464,7 @@ class WanTransformer3DModel:
         return self.load_state_dict(out)
 
     @classmethod
-    def from_pretrained(cls, path: str, device="cuda:0", comm=None, subfolder: str = "transformer"):
+    def from_pretrained(cls, path: str, device="cuda:0", comm=None, subfolder: str = "transformer", linear_precision: str = "bf16"):
         """The `transformer/` component of a local diffusers Wan2.1-I2V checkpoint directory (what
         `WanImageToVideoPipeline.from_pretrained(model_id, ...)` loads at INFER:191-197): `config.json` (diffusers field names:
         num_attention_heads x attention_head_dim, ffn_dim, num_layers, in_channels, out_channels, text_dim, freq_dim, image_dim,
@@ -428,7 +484,7 @@ class WanTransformer3DModel:
                             out_dim=int(c.get("out_channels", cfg.out_dim)), freq_dim=int(c.get("freq_dim", cfg.freq_dim)),
                             text_dim=int(c.get("text_dim", cfg.text_dim)), img_dim=int(c.get("image_dim") or cfg.img_dim),
                             patch_size=tuple(c.get("patch_size", cfg.patch_size)), eps=float(c.get("eps", cfg.eps)))
-        return cls(cfg, device, comm=comm).load_diffusers_state_dict(checkpoint.load_dir(folder))
+        return cls(cfg, device, comm=comm, linear_precision=linear_precision).load_diffusers_state_dict(checkpoint.load_dir(folder))
 
     def init_random(self, seed: int = 0):
         """Synthetic weights of the right shapes, generated directly on the device: there are no checkpoints
@@ -672,7 +728,7 @@ class WanTransformer3DModel:
         forwards; the velocity lands in result[0].  share / role: the two forwards of a CFG pair (forward_tokens_pair) -- the "produce"
         forward copies its residual stream after layer 0's self-attention block into share["x"], the "consume" forward starts from it
         instead of computing the patch embedding and that block again."""
-        cfg, W, dev = self.cfg, self.w, self.device
+        cfg, W, dev = self.cfg, self._wl, self.device
         _buf = lambda name, shape, dtype, zero=False: self._buf(name + tag, shape, dtype, zero)  # noqa: E731
         bf, f32 = torch.bfloat16, torch.float32
         Cin, T, Hh, Ww = x_in.shape

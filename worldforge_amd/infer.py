@@ -76,7 +76,7 @@ def run(models_dir: Optional[str], video_ref: str, model: str = "720p", output: 
         prompt: Optional[str] = None, negative_prompt: Optional[str] = None, embeds: Optional[str] = None,
         use_pca_channel_selection: bool = False, soften_mask: bool = False, transition_distance: int = 15, decay_type: str = "sine",
         save_png: bool = False, device: str = "cuda:0", components: Optional[dict] = None, max_area: Optional[int] = None, seed: int = 42,
-        vae_precision: str = "fp16x3", flow_backend: str = "farneback"):
+        vae_precision: str = "fp16x3", flow_backend: str = "farneback", dit_precision: str = "bf16"):
     """INFER:153-339.  Returns (frames float32 [F,H,W,3] in [0,1], output directory of the PNG frames or None).
     components: {"transformer", "vae", "scheduler"} to use instead of loading `models_dir` (tests; synthetic weights); max_area overrides the
     model's pixel budget the same way harness.prepare_inputs documents."""
@@ -92,7 +92,7 @@ def run(models_dir: Optional[str], video_ref: str, model: str = "720p", output: 
         if not os.path.exists(model_path):
             raise ValueError(f"Model path does not exist: {model_path}")
         vae = AutoencoderKLWan.from_pretrained(model_path, device=dev, precision=vae_precision)                              # INFER:185-189
-        transformer = WanTransformer3DModel.from_pretrained(model_path, device=dev)                                          # INFER:191-197
+        transformer = WanTransformer3DModel.from_pretrained(model_path, device=dev, linear_precision=dit_precision)                # INFER:191-197
         cfg_file = os.path.join(model_path, "scheduler", "scheduler_config.json")
         sconf = json.load(open(cfg_file)) if os.path.exists(cfg_file) else {"flow_shift": 3.0 if model == "480p" else 5.0}
         scheduler = UniPCMultistepScheduler.from_config(sconf, flow_backend=flow_backend)                                    # INFER:200-202
@@ -166,13 +166,16 @@ def main(argv=None):
     ap.add_argument("--negative-prompt", default=None, help="default: the reference's static / dynamic negative prompt by --static (INFER:277-285)")
     ap.add_argument("--embeds", default=None, help=".npz / .safetensors with prompt_embeds, negative_prompt_embeds, image_embeds")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--dit-precision", choices=["bf16", "mxfp8"], default="bf16",
+                    help="DiT block linears: bf16 (default) or the opt-in MX-fp8 GEMMs (lower precision, faster)")
     a = ap.parse_args(argv)
     frames, png_dir = run(a.models_dir, a.video_ref, model=a.model, output=a.output, image=a.image, guided=a.guided,
                           resample_steps=a.resample_steps, guide_steps=a.guide_steps, omega=a.omega, omega_resample=a.omega_resample,
                           num_frames=a.num_frames, num_inference_steps=a.num_inference_steps, guidance_scale=a.guidance_scale,
                           resample_round=a.resample_round, static=a.static == "True", prompt=a.prompt, negative_prompt=a.negative_prompt,
                           embeds=a.embeds, use_pca_channel_selection=a.use_pca_channel_selection, soften_mask=a.soften_mask,
-                          transition_distance=a.transition_distance, decay_type=a.decay_type, save_png=a.save_png, device=a.device)
+                          transition_distance=a.transition_distance, decay_type=a.decay_type, save_png=a.save_png, device=a.device,
+                          dit_precision=a.dit_precision)
     print(f"{len(frames)} frames -> {png_dir}")
 
 

@@ -28,7 +28,8 @@ import torch
 
 from . import ops
 from ._ffi import WF_BF16, WF_F32, call
-from .dit import EPI_BF16, EPI_BF16_GELU, EPI_F32, EPI_F32_ACC, _pad64, attention, attention_exchange, gemm, head_max_norm2
+from .dit import (EPI_BF16, EPI_BF16_GELU, EPI_F32, EPI_F32_ACC, _pad64, attention, attention_exchange, gemm, head_max_norm2,
+                  quantize_linears)
 
 
 @dataclass
@@ -121,7 +122,14 @@ def fold_lora(sd: Dict[str, torch.Tensor], lora_sd: Dict[str, torch.Tensor], mul
 class LongCatVideoTransformer3DModel:
     dtype = torch.bfloat16
 
-    def __init__(self, cfg: LongCatConfig, device="cuda:0", enable_bsa: bool = False, bsa_params: Optional[dict] = None, comm=None):
+    # the per-block token GEMMs that linear_precision="mxfp8" runs in MX-fp8 (embeddings, AdaLN, final layer and the caption K / V stay bf16)
+    MX_LINEARS = ("attn.qkv.w", "attn.proj.w", "cross_attn.q_linear.w", "cross_attn.proj.w", "ffn.w13", "ffn.w2")
+
+    def __init__(self, cfg: LongCatConfig, device="cuda:0", enable_bsa: bool = False, bsa_params: Optional[dict] = None, comm=None,
+                 linear_precision: str = "bf16"):
+        if linear_precision not in ("bf16", "mxfp8"):
+            raise ValueError(f"linear_precision must be 'bf16' or 'mxfp8', not {linear_precision!r}")
+        self.linear_precision = linear_precision
         assert cfg.hidden_size // cfg.num_heads == 128 and cfg.hidden_size % cfg.num_heads == 0, "attention kernel is built for head_dim 128"
         assert cfg.patch_size == (1, 2, 2)
         self.cfg = cfg
@@ -137,6 +145,19 @@ class LongCatVideoTransformer3DModel:
         self._bsa = bool(enable_bsa)
         self.bsa_params = dict(bsa_params) if bsa_params else dict(sparsity=0.875, chunk_3d_shape_q=[4, 4, 8], chunk_3d_shape_k=[4, 4, 8])  # bsa_interface.py:618-621 defaults
         self.last_bsa_indices = None
+
+    @property
+    def w(self) -> Dict[str, torch.Tensor]:
+        return self._w
+
+    @w.setter
+    def w(self, W: Dict[str, torch.Tensor]):
+        self._w = W
+        self.weights_changed()
+
+    def weights_changed(self):
+        """Call after editing weight tensors IN PLACE: re-derives the MX-fp8 copies of linear_precision="mxfp8" (none in bf16)."""
+        self._wl = quantize_linears(self._w, self.MX_LINEARS) if self.linear_precision == "mxfp8" else self._w
 
     def enable_bsa(self):
         """LCD:270-272."""
@@ -321,7 +342,7 @@ class LongCatVideoTransformer3DModel:
         attention kernel (segment addressing), the 64-column output rows are gathered at the end.  The condition / noise split of
         LCA:123-138 is by GLOBAL token index: a rank's rows below the first frame boundary are condition queries (keys < nc), the rest
         noise queries."""
-        cfg, W, dev = self.cfg, self.w, self.device
+        cfg, W, dev = self.cfg, self._wl, self.device
         bf, f32 = torch.bfloat16, torch.float32
         Cin, T, Hh, Ww = x_in.shape
         assert Cin == cfg.in_channels and len(timesteps) == T

@@ -279,3 +279,27 @@ def flow_metrics(ref_flow: torch.Tensor, chan_flow: torch.Tensor, variant: int =
     call("wf_flow_metrics_variant", ref_flow.data_ptr(), chan_flow.data_ptr(), sim.data_ptr(), n, Tm, Cr, Cc, h * w, variant,
          ws.data_ptr(), stream())
     return sim
+
+
+def mx_quant(x: torch.Tensor, q: Optional[torch.Tensor] = None, s: Optional[torch.Tensor] = None):
+    """OCP MX-fp8 quantization of a bf16 matrix x [M, K] (unit column stride, any row stride): e4m3 elements q [M, K] and E8M0 block
+    scales s [M, K/32] (uint8 views; one scale per 32 consecutive elements of a row) -- wf_mx_quant_e4m3."""
+    assert x.dim() == 2 and x.dtype == torch.bfloat16 and x.stride(1) == 1
+    M, K = x.shape
+    q = torch.empty((M, K), dtype=torch.uint8, device=x.device) if q is None else q
+    s = torch.empty((M, K // 32), dtype=torch.uint8, device=x.device) if s is None else s
+    assert q.shape == (M, K) and q.is_contiguous() and s.shape == (M, K // 32) and s.is_contiguous()
+    call("wf_mx_quant_e4m3", x.data_ptr(), q.data_ptr(), s.data_ptr(), M, K, x.stride(0), stream())
+    return q, s
+
+
+def gemm_mxfp8(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor,
+               epi: int, gate: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[M,N] = epi(dequant(xq, xs) @ dequant(wq, ws)^T + bias) on the scaled MX MFMA (wf_gemm_mxfp8); K % 128 == 0."""
+    M, K = xq.shape
+    N = wq.shape[0]
+    assert wq.shape[1] == K and xs.shape == (M, K // 32) and ws.shape == (N, K // 32) and out.shape[0] == M and out.shape[1] == N
+    assert xs.is_contiguous() and ws.is_contiguous()
+    call("wf_gemm_mxfp8", xq.data_ptr(), xs.data_ptr(), wq.data_ptr(), ws.data_ptr(), bias.data_ptr() if bias is not None else None,
+         out.data_ptr(), gate.data_ptr() if gate is not None else None, M, N, K, xq.stride(0), wq.stride(0), out.stride(0), epi, stream())
+    return out
