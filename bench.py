@@ -1,6 +1,10 @@
 """bench.py -- denoising steps/s of the IRR/FLF/DSG guided sampler (Wan2.1-I2V-14B, 81 frames x 480x832) on MI355X.
 
 Contract (driver):  python bench.py --gpus N --steps K --warmup W   ->  ONE JSON line on rank 0.
+Such a plain run does what the headline figure needs and no more: set-up, the warm-up steps, the timed window (with the HIP events the
+`roofline` and `hbm` fields are read from), the optional --dump-outputs, the line.  Every measurement that takes runs of its own -- the CPU
+baseline, the `also` windows of the other configurations and VAE precision, the smoke job against the oracle, the box calibration around the
+window with `value_normalised`, the max-tracking attention body, the FLF gate cost -- is behind --full.
 For N > 1 the driver launches one rank per GPU with torch.distributed.run; the DiT token sequence is sharded over ranks
 (K/V all-gather over RCCL, see worldforge_amd/parallel.py) -- "strong" scaling: the job (one video) is fixed.
 
@@ -68,7 +72,11 @@ def main(argv=None):
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=832)
     ap.add_argument("--layers", type=int, default=40, help="DiT depth (40 = Wan2.1-14B; smaller only for debugging -> flagged)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline window, everything else this benchmark measures, each in runs of its own around or after the "
+                         "window: `cpu_baseline`, the `also` windows (720p, LongCat, the TF32-class VAE with the smoke job's PSNR against the CPU "
+                         "oracle), `box_calib_tflops` / `value_normalised`, `roofline.tracked_body_*`, `flf_gate_ms` (minutes; off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave `cpu_baseline` out")
     ap.add_argument("--flow-backend", default="farneback", choices=["tdiff", "farneback"],
                     help="FLF motion backend: farneback (default) = what the installed reference executes, as the GPU restatement of "
                          "cv2.calcOpticalFlowFarneback (parity with a real cv2 unpinned); tdiff = the branch the reference runs only "
@@ -102,8 +110,8 @@ def main(argv=None):
                          "(default): time a few real-width layers with every candidate on THIS node before the timed window and keep the "
                          "fastest (the line carries `exchange` with the timings)")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the short windows of BASELINE configs 3 (720p) and 4 (LongCat distilled + refine step) that the default "
-                         "1-GPU run appends to the line as `also`")
+                    help="with --full: skip the short windows of BASELINE configs 3 (720p) and 4 (LongCat distilled + refine step) that a "
+                         "1-GPU --full run appends to the line as `also`")
     ap.add_argument("--workload", default="wan", choices=["wan", "longcat"],
                     help="wan = the BASELINE metric (default); longcat = the same contract on LongCat-Video 13.6B guided i2v (config 4's model)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -213,8 +221,9 @@ def main(argv=None):
         if phase == "begin" and idx < Wm:
             progress(f"warm-up step {idx + 1} of {Wm} (schedule step {i})")
         if phase == "begin" and idx == Wm:
-            torch.cuda.synchronize()
-            marks["calib0"] = box_calib_tflops(device)   # outside the timed window, on a chip the warm-up steps have heated
+            if a.full:
+                torch.cuda.synchronize()
+                marks["calib0"] = box_calib_tflops(device)   # outside the timed window, on a chip the warm-up steps have heated
             barrier()
             progress(f"timed window starts: {K} steps")
             marks["t0"] = time.perf_counter()
@@ -231,7 +240,8 @@ def main(argv=None):
             barrier()
             marks["t1"] = time.perf_counter()
             progress(f"timed window ends: {marks['t1'] - marks['t0']:.1f} s")
-            marks["calib1"] = box_calib_tflops(device)
+            if a.full:
+                marks["calib1"] = box_calib_tflops(device)
 
     gen = torch.manual_seed(42)
     result = pipe(image=image, height=a.height, width=a.width, num_frames=a.frames, num_inference_steps=50, guidance_scale=4.0,
@@ -373,7 +383,7 @@ def main(argv=None):
                                **attn_pmc_fields(kern, L, cfg.num_heads, world, a.as_rank_of > 1),
                                "launches": len(attn_ms), "avg_launch_ms": avg,
                                "flop_per_launch": attn_flop}
-            if kern == "k_attn_w4<4>" and world == 1 and a.as_rank_of <= 1:
+            if a.full and kern == "k_attn_w4<4>" and world == 1 and a.as_rank_of <= 1:
                 tms = tracked_body_ms(model, L, cfg.num_heads)
                 if tms:
                     out["roofline"]["tracked_body_avg_launch_ms"] = tms
@@ -384,7 +394,7 @@ def main(argv=None):
             us, nb = sum(u for u, _ in blend) / len(blend), blend[0][1]
             out["hbm"] = {"kernel": "k_blend4_rgb (wf_blend_pixels, SCHED:1375-1380)", "bytes": nb, "avg_us": us, "launches": len(blend),
                           "achieved_GBps": nb / us / 1e3, "peak_GBps": 8000.0, "frac_of_8TBps": nb / us / 1e3 / 8000.0}
-        if world == 1 and a.as_rank_of <= 1:
+        if a.full and world == 1 and a.as_rank_of <= 1:
             out["flf_gate_ms"] = flf_gate_ms(sch, (1, 16, T, a.height // 8, a.width // 8), device)
         if per_rank is not None and plain_ms:
             # one DiT layer of one forward on this rank ~ plain step / (2 forwards x layers); the K / V^T exchange is meant to hide under
@@ -400,13 +410,13 @@ def main(argv=None):
                       file=sys.stderr)
         if a.layers != 40:
             out["invalid_reason"] = f"debug run with {a.layers} DiT layers (the named model has 40)"
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             cb = cpu_baseline(L, a.frames, a.height, a.width)
             ng, npl = len(guided_ms), len(plain_ms)
             t_cpu = (ng * 4 + npl * 2) * cb["t_dit_forward_s"] + ng * 2 * cb["t_vae_roundtrip_s"]
             out["cpu_baseline"] = {"value": K / t_cpu, "unit": "steps/s", "cores": cb["cores"], "kind": "port", "sample": cb["sample"]}
         default_job = (a.frames, a.height, a.width, a.layers) == (81, 480, 832, 40)
-        if world == 1 and a.as_rank_of <= 1 and not a.no_also and default_job:
+        if a.full and world == 1 and a.as_rank_of <= 1 and not a.no_also and default_job:
             # BASELINE configs 3 and 4 on the driver's own box (headline keys above are final; these are short extra windows)
             also = []
             model._ws.clear()

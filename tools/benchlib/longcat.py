@@ -210,7 +210,7 @@ def main_longcat(a):
                                "traffic": None, "launches": len(attn_ms), "avg_launch_ms": avg, "flop_per_launch": flop}
         if cfg.depth != 48:
             out["invalid_reason"] = f"debug run with {cfg.depth} DiT blocks (the named model has 48)"
-        if not a.no_cpu_baseline and world == 1 and a.as_rank_of <= 1:
+        if a.full and not a.no_cpu_baseline and world == 1 and a.as_rank_of <= 1:
             cb = cpu_baseline_longcat()
             C, Hd = cfg.hidden_size, cfg.ffn_hidden
             fwd = cfg.depth * (2.0 * L * C * (6 * C + 3 * Hd) + 4.0 * L * L * C)
