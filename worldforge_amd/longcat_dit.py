@@ -12,8 +12,8 @@ Numerics: bf16 weights, bf16 residual stream (LCD:104, 120), bf16 GEMM / attenti
 embedding and AdaLN parameters (LCD:84-88, 310-311: the fp32 activations are fed to the bf16 MFMA GEMM as a hi + lo bf16 pair, which
 keeps 16 mantissa bits), fp32 LayerNorm statistics, fp32 final projection (LCB:162-167).
 
-Runtime LoRA (LCD:189-268) is offered as a weight fold at load (`fold_lora`).  Not covered here (next rows of SURVEY section 8f):
-KV-cache continuation (LCA:147-181), block-sparse attention (LCA:57-66), sequence parallelism.
+Runtime LoRA (LCD:189-268) is offered as a weight fold at load (`fold_lora`).  Block-sparse attention (LCA:57-66; `enable_bsa`, bsa.py)
+and sequence parallelism (`comm`, parallel.py) are built.  Not covered here: KV-cache continuation (LCA:147-181).
 """
 from __future__ import annotations
 
