@@ -182,6 +182,15 @@ int wf_mx_quant_e4m3(const void* X, void* Q, void* S, int M, int K, int ldx, voi
  * K % 128 == 0, N % 4 == 0; anything else returns WF_EINVAL. */
 int wf_gemm_mxfp8(const void* Xq, const void* Xs, const void* Wq, const void* Ws, const float* bias, void* out, const float* gate, int M, int N,
                   int K, int ldx, int ldw, int ldo, int epilogue, void* stream);
+/* Switchable LoRA adapters on resident weights (csrc/lora.hip; longcat_video_dit.py:194-270, lora_utils.py:15-78 as a weight switch):
+ *   out[n,k] = bf16_rne(base[n,k] + sum_j scale_j * sum_r U_j[n,r] * D_j[(n / (N / nsep_j)) * rank_j + r, k]),  j < n_adapters (1..4)
+ * for one bf16 matrix [N, K] or a contiguous row slice of one (contiguous rows, K % 8 == 0).  U_j bf16 [N, rank_j], D_j bf16
+ * [nsep_j * rank_j, K] (row block b of a fused qkv / kv weight uses rank slice b: LoRAUPParallel), rank_j a multiple of 8 in 8..256,
+ * N % nsep_j == 0, all pointers 16-byte aligned.  bf16 MFMA products, fp32 accumulation / scaling / base add, ONE rounding.  base is
+ * only read; out may be base.  The slots j >= n_adapters are ignored.  Anything else returns WF_EINVAL before any device work. */
+int wf_lora_fold(const void* base, void* out, int N, int K, int n_adapters, const void* U0, const void* D0, int rank0, int nsep0,
+                 float scale0, const void* U1, const void* D1, int rank1, int nsep1, float scale1, const void* U2, const void* D2,
+                 int rank2, int nsep2, float scale2, const void* U3, const void* D3, int rank3, int nsep3, float scale3, void* stream);
 
 /* flash_attention (attention.py:24-130) as used by model.py:149-154 (self) and :220-222 (cross): fused
  * softmax(Q K^T * softmax_scale) V, no mask, head_dim 128.  Q [H][Lq][128], K [H][Lkp][128] (rows >= kv_len zero),

@@ -32,6 +32,7 @@ SOURCES = {
     "flow.hip": ["-ffp-contract=off"],
     "gemm.hip": [],
     "mxfp8.hip": [],
+    "lora.hip": [],
     "attention.hip": [],
     "dit_ops.hip": [],
     "longcat_ops.hip": ["-ffp-contract=off"],

@@ -12,7 +12,10 @@ Numerics: bf16 weights, bf16 residual stream (LCD:104, 120), bf16 GEMM / attenti
 embedding and AdaLN parameters (LCD:84-88, 310-311: the fp32 activations are fed to the bf16 MFMA GEMM as a hi + lo bf16 pair, which
 keeps 16 mantissa bits), fp32 LayerNorm statistics, fp32 final projection (LCB:162-167).
 
-Runtime LoRA (LCD:189-268) is offered as a weight fold at load (`fold_lora`).  Block-sparse attention (LCA:57-66; `enable_bsa`, bsa.py)
+Runtime LoRA (LCD:189-270): `load_lora` / `enable_loras` / `disable_all_loras` keep the adapters' bf16 factors resident and SWITCH the
+weights on the GPU (csrc/lora.hip: effective = bf16(base + sum of the active adapters' scaled products), one rounding, from an untouched
+base copy), so the forward still runs on plain bf16 matrices and a LoRA costs nothing per step; `fold_lora` is the host-side state-dict
+route (a fold before load_state_dict, not undoable).  Block-sparse attention (LCA:57-66; `enable_bsa`, bsa.py)
 and sequence parallelism (`comm`, parallel.py) are built.  Not covered here: KV-cache continuation (LCA:147-181).
 """
 from __future__ import annotations
@@ -119,6 +122,20 @@ def fold_lora(sd: Dict[str, torch.Tensor], lora_sd: Dict[str, torch.Tensor], mul
     return out
 
 
+_LORA_H = "___lorahyphen___"
+
+
+@dataclass(eq=False)
+class LoRAPart:
+    """One wrapped Linear of one adapter, placed in this model's fused storage: rows [row0, row0 + U.shape[0]) of matrix `wkey`."""
+    wkey: str
+    row0: int
+    U: torch.Tensor      # bf16 [rows, rank]: the up-projection, its separate blocks stacked (never block-diagonal)
+    D: torch.Tensor      # bf16 [nsep * rank, K]: the down-projection; row block b of the slice uses rank slice b
+    nsep: int
+    scale: float         # multiplier * alpha_scale
+
+
 class LongCatVideoTransformer3DModel:
     dtype = torch.bfloat16
 
@@ -137,6 +154,11 @@ class LongCatVideoTransformer3DModel:
         self.cp_split_hw = None
         self.comm = comm  # parallel.Comm (or a stand-in): sequence parallelism over contiguous token shards, see forward_tokens
         self.device = torch.device(device)
+        # switchable LoRA adapters (LCD:189-270): lora_dict key -> [LoRAPart], active_loras the enabled keys in order; _eff holds ONE
+        # effective buffer per touched matrix, allocated at its first activation and reused by every later switch
+        self.lora_dict: Dict[str, list] = {}
+        self.active_loras: list = []
+        self._eff: Dict[str, torch.Tensor] = {}
         self.w: Dict[str, torch.Tensor] = {}
         self._ws = {}
         self._rope = {}
@@ -148,16 +170,156 @@ class LongCatVideoTransformer3DModel:
 
     @property
     def w(self) -> Dict[str, torch.Tensor]:
+        """The weights the forward runs on: the base dictionary itself while no adapter is active, else the effective dictionary
+        (touched matrices replaced by their effective buffers, every other tensor shared with the base)."""
         return self._w
 
     @w.setter
     def w(self, W: Dict[str, torch.Tensor]):
-        self._w = W
+        """A new base: every adapter is deactivated (the loaded ones stay in lora_dict), the effective buffers are dropped."""
+        self._base = self._w = W
+        self.active_loras = []
+        self._eff = {}
         self.weights_changed()
 
+    @property
+    def base_w(self) -> Dict[str, torch.Tensor]:
+        """The base weights (never written by a LoRA switch)."""
+        return self._base
+
     def weights_changed(self):
-        """Call after editing weight tensors IN PLACE: re-derives the MX-fp8 copies of linear_precision="mxfp8" (none in bf16)."""
+        """Call after editing (base) weight tensors IN PLACE: with adapters active the effective weights are folded again from the
+        base, then the MX-fp8 copies of linear_precision="mxfp8" are re-derived (none in bf16)."""
+        try:
+            self._w = self._fold_active() if self.active_loras else self._base
+        except Exception:  # a switch that cannot be made leaves the base model, not half-folded buffers
+            self.active_loras, self._w = [], self._base
+            self._wl = quantize_linears(self._w, self.MX_LINEARS) if self.linear_precision == "mxfp8" else self._w
+            raise
         self._wl = quantize_linears(self._w, self.MX_LINEARS) if self.linear_precision == "mxfp8" else self._w
+
+    # ---- LoRA adapters (LCD:189-270, lora_utils.py) ---------------------------------------------------------------
+    def _lora_target(self, module: str):
+        """Reference module name -> (key in the fused storage, first row, rows) of its Linear; KeyError if the model has none."""
+        cfg, W = self.cfg, self._base
+        parts = module.split(".")
+        key = row0 = rows = None
+        if len(parts) == 4 and parts[0] == "blocks" and parts[1].isdigit() and parts[2] == "ffn" and parts[3] in ("w1", "w3"):
+            key, rows = f"blocks.{parts[1]}.ffn.w13", cfg.ffn_hidden
+            row0 = 0 if parts[3] == "w1" else rows
+        elif len(parts) == 4 and parts[0] == "blocks" and parts[1].isdigit() and parts[2:] == ["adaLN_modulation", "1"]:
+            key, rows = "ada.w", 6 * cfg.hidden_size
+            row0 = int(parts[1]) * rows
+            if int(parts[1]) >= cfg.depth:
+                key = None
+        elif parts[-2:] == ["ffn", "w2"]:
+            key, row0 = module, 0
+        elif module != "x_embedder.proj":  # (a Conv3d in the reference: not a Linear, never wrapped)
+            key, row0 = module + ".w", 0
+        t = W.get(key) if key is not None else None
+        if t is None or t.dim() != 2 or t.dtype != torch.bfloat16:
+            raise KeyError(f"LoRA entry {module} has no Linear {module}.weight in the model")
+        return key, row0, (t.shape[0] if rows is None else rows)
+
+    def _parse_lora(self, lora_sd, multiplier, network_dim, network_alpha):
+        """State dict in the reference's naming -> [LoRAPart] on the device, factors rounded to bf16 (LCD:221); the naming and the
+        strictness of fold_lora."""
+        dev, bf = self.device, torch.bfloat16
+        out = []
+        for key in lora_sd:
+            if not key.endswith(".lora_down.weight"):
+                continue
+            name = key[: -len(".lora_down.weight")]
+            module = name.replace("lora" + _LORA_H, "").replace(_LORA_H, ".")
+            wkey, row0, rows = self._lora_target(module)
+            K = self._base[wkey].shape[1]
+            down = lora_sd[key]
+            if name + ".alpha_scale" in lora_sd:
+                scale = float(lora_sd[name + ".alpha_scale"])
+            else:
+                scale = (network_alpha or network_dim) / network_dim
+            if name + ".lora_up.weight" in lora_sd:
+                ups = [lora_sd[name + ".lora_up.weight"]]
+            else:
+                ups = [lora_sd[k] for k in sorted((k for k in lora_sd if k.startswith(name + ".lora_up.blocks.")),
+                                                  key=lambda k: int(k.split(".")[-2]))]
+                if not ups:
+                    raise KeyError(f"LoRA entry {name} has no up-projection")
+            nsep = len(ups)
+            rank = down.shape[0] // nsep if down.dim() == 2 else 0
+            ok = (down.dim() == 2 and down.shape[1] == K and rank > 0 and down.shape[0] == nsep * rank
+                  and all(u.dim() == 2 and tuple(u.shape) == (rows // nsep, rank) for u in ups) and rows % nsep == 0)
+            if not ok:
+                raise ValueError(f"LoRA update for {module}.weight: down {tuple(down.shape)}, up {[tuple(u.shape) for u in ups]} do not "
+                                 f"give the weight's shape {(rows, K)}")
+            U = torch.cat([u.to(torch.float32) for u in ups], 0).to(bf)
+            D = down.to(torch.float32).to(bf)
+            if rank % 8:  # the kernel takes ranks in whole 8-element operand slots: zero ranks change nothing
+                pad = 8 - rank % 8
+                U = torch.nn.functional.pad(U, (0, pad))
+                D = torch.nn.functional.pad(D.view(nsep, rank, K), (0, 0, 0, pad)).reshape(nsep * (rank + pad), K)
+            out.append(LoRAPart(wkey, row0, U.contiguous().to(dev), D.contiguous().to(dev), nsep, float(multiplier) * scale))
+        return out
+
+    def load_lora(self, lora, lora_key: str, multiplier: float = 1.0, lora_network_dim: int = 128, lora_network_alpha: float = 64):
+        """LCD:194-215.  lora: a .safetensors path or a state dict in the reference's naming (`lora___lorahyphen___blocks___lorahyphen___3
+        ___lorahyphen___attn___lorahyphen___qkv.lora_down.weight`, `.lora_up.weight` or `.lora_up.blocks.N.weight`, optional
+        `.alpha_scale`, else alpha / dim).  The factors are rounded to bf16, uploaded once and stay resident.  KeyError for an entry
+        whose Linear the model does not have, ValueError for a shape mismatch, both raised here with lora_dict unchanged.  Loading
+        under an existing key replaces that adapter (the weights are folded again if it is active)."""
+        if isinstance(lora, (str, os.PathLike)):
+            from .checkpoint import load_file
+            lora = load_file(os.fspath(lora))
+        parts = self._parse_lora(lora, multiplier, lora_network_dim, lora_network_alpha)
+        self.lora_dict[lora_key] = parts
+        if lora_key in self.active_loras:
+            self.weights_changed()
+
+    def enable_loras(self, lora_key_list):
+        """LCD:217-247: disable_all_loras(), then the listed keys become active (unknown keys are ignored, LCD:219): every touched matrix
+        becomes wf_lora_fold(base, all its active adapters) in its effective buffer; the forward's cost does not change."""
+        active = []
+        for k in lora_key_list:
+            if k in self.lora_dict and k not in active:
+                active.append(k)
+        self.active_loras = active
+        self.weights_changed()
+
+    def disable_all_loras(self):
+        """LCD:249-268: the forward reads the base tensors again (the effective buffers are kept for the next switch)."""
+        self.active_loras = []
+        self.weights_changed()
+
+    def _fold_active(self) -> Dict[str, torch.Tensor]:
+        """The effective dictionary of the active adapters, folded from the base on the device."""
+        touched: Dict[str, Dict[int, list]] = {}
+        for key in self.active_loras:
+            for part in self.lora_dict[key]:
+                touched.setdefault(part.wkey, {}).setdefault(part.row0, []).append(part)
+        eff = dict(self._base)
+        for wkey, slices in touched.items():
+            base = self._base.get(wkey)
+            for row0, parts in slices.items():
+                for q in parts:
+                    if base is None or base.dim() != 2 or row0 + q.U.shape[0] > base.shape[0] or q.D.shape[1] != base.shape[1]:
+                        raise ValueError(f"LoRA adapter for {wkey} rows {row0}..{row0 + q.U.shape[0]} does not fit the current base weights")
+            buf = self._eff.get(wkey)
+            if buf is None or buf.shape != base.shape or buf.device != base.device:
+                buf = self._eff[wkey] = torch.empty_like(base)
+            pos = 0
+            for row0 in sorted(slices):  # rows no active adapter touches are the base's bits
+                if row0 > pos:
+                    buf[pos:row0].copy_(base[pos:row0])
+                parts = slices[row0]
+                rows = parts[0].U.shape[0]
+                for i in range(0, len(parts), 4):  # one launch, ONE rounding for up to 4 adapters of a Linear; a fifth rounds again
+                    ops.lora_fold((base if i == 0 else buf)[row0:row0 + rows], buf[row0:row0 + rows],
+                                  [(q.U, q.D, q.nsep, q.scale) for q in parts[i:i + 4]])
+                pos = row0 + rows
+            if pos < base.shape[0]:
+                buf[pos:].copy_(base[pos:])
+            eff[wkey] = buf
+        return eff
 
     def enable_bsa(self):
         """LCD:270-272."""

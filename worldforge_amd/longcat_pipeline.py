@@ -89,8 +89,9 @@ class LongCatVideoPipeline:
                         image=None, num_cond_frames: int = 0, num_inference_steps: int = 50, generator=None, output_type: str = "np",
                         t_thresh: float = 0.5, spatial_refine_only: bool = False, step_hook=None):
         """The 720p refine pass: the stage-1 (480p) video is up-sampled, encoded, mixed with noise at t_thresh and denoised from there
-        without CFG, the DiT running with block-sparse self-attention (enable it on the DiT, with the refinement LoRA folded in, as
-        run_longcat_worldforge_single.py:447-451 does).  stage1_video: uint8 frames [F, H0, W0, 3] (tensor / array / list of arrays);
+        without CFG, the DiT running with block-sparse self-attention and the refinement LoRA, as
+        run_longcat_worldforge_single.py:447-451 does: `dit.enable_loras(["refinement_lora"])` and `dit.enable_bsa()` on the resident
+        model that ran stage 1 (longcat_dit.load_lora / enable_loras; or a model built with the adapter folded in by fold_lora).  stage1_video: uint8 frames [F, H0, W0, 3] (tensor / array / list of arrays);
         image: the conditioning first frame at the target size or None.  Returns frames [1, F', H, W, 3] in [0, 1]."""
         import math
 

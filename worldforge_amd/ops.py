@@ -303,3 +303,25 @@ def gemm_mxfp8(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.T
     call("wf_gemm_mxfp8", xq.data_ptr(), xs.data_ptr(), wq.data_ptr(), ws.data_ptr(), bias.data_ptr() if bias is not None else None,
          out.data_ptr(), gate.data_ptr() if gate is not None else None, M, N, K, xq.stride(0), wq.stride(0), out.stride(0), epi, stream())
     return out
+
+
+def lora_fold(base: torch.Tensor, out: torch.Tensor, adapters) -> torch.Tensor:
+    """out = bf16(base + sum_j scale_j * U_j @ D_j[row block's rank slice]) for one bf16 matrix [N, K] or a contiguous row slice of one
+    (wf_lora_fold): adapters = 1..4 tuples (U bf16 [N, rank], D bf16 [nsep * rank, K], nsep, scale); fp32 accumulation, one rounding.
+    base is only read; out may be base."""
+    if not (base.is_cuda and out.is_cuda and all(U.is_cuda and D.is_cuda for U, D, _, _ in adapters)):
+        raise RuntimeError("worldforge_amd ops need device tensors (there is no CPU fallback)")
+    assert base.dim() == 2 and base.dtype == out.dtype == torch.bfloat16 and base.shape == out.shape
+    assert base.is_contiguous() and out.is_contiguous()
+    N, K = base.shape
+    flat = []
+    for U, D, nsep, scale in adapters:
+        assert U.dtype == D.dtype == torch.bfloat16 and U.is_contiguous() and D.is_contiguous()
+        assert U.shape[0] == N and D.shape == (int(nsep) * U.shape[1], K), (tuple(U.shape), tuple(D.shape), nsep, (N, K))
+        flat += [U.data_ptr(), D.data_ptr(), U.shape[1], int(nsep), float(scale)]
+    n = len(flat) // 5
+    if not 1 <= n <= 4:
+        raise ValueError(f"wf_lora_fold takes 1..4 adapters per launch, not {n}")
+    flat += [None, None, 0, 0, 0.0] * (4 - n)
+    call("wf_lora_fold", base.data_ptr(), out.data_ptr(), N, K, n, *flat, stream())
+    return out
