@@ -141,6 +141,40 @@ def test_gemm_layout_exact(M, N, K):
     assert torch.equal(got2, want.T)
 
 
+@pytest.mark.parametrize("M,N,K", [(1100, 3820, 128), (1100, 3820, 384), (300, 264, 128)])
+def test_mx_and_bf16_epilogues_agree_bit_for_bit(M, N, K):
+    """wf_gemm_mxfp8 and wf_gemm_bf16 share one epilogue (csrc/gemm_pp.h); here they must give the same bits.  X in [-4, 4] and W in
+    [-2, 2] are small integers: at most two mantissa bits, so the MX quantizer represents them exactly under any power-of-two block scale
+    (asserted), and every dot product is an integer below 2^24, exact in fp32 in any summation order -- both kernels hand their epilogues
+    the same accumulator bits.  Shapes: ragged M and N with N % 8 == 4 (the half-chunk store) where the bf16 call takes the ping-pong
+    kernel, at one K tile of the MX kernel and at three; and a small problem where the bf16 call takes the 128 x 128 k_gemm, whose
+    untransposed epilogue must give the same bits too.  Outputs are strided views with guard rows and columns."""
+    from worldforge_amd import dit
+    g = torch.Generator().manual_seed(M + N + K)
+    x = torch.randint(-4, 5, (M, K), generator=g).to(BF)
+    w = torch.randint(-2, 3, (N, K), generator=g).to(BF)
+    bias, gate = torch.randn(N, generator=g), torch.randn(N, generator=g)
+    ldo = (N + 15) // 8 * 8  # guard columns; a multiple of 8 keeps the view below the guard row 16-byte aligned in bf16
+    old = torch.randn(M + 2, ldo, generator=g)
+    xd, wd, bias_d, gate_d = x.to(DEV), w.to(DEV), bias.to(DEV), gate.to(DEV)
+    xq, xs = ops.mx_quant(xd)
+    wq, ws = ops.mx_quant(wd)
+    torch.cuda.synchronize()
+    assert torch.equal(dequant(xq, xs), x.double()) and torch.equal(dequant(wq, ws), w.double())
+    guard = torch.ones(M + 2, ldo, dtype=torch.bool)
+    guard[1:M + 1, :N] = False
+    for epi in (0, 1, 2, 3):
+        init = old.to(BF if epi < 2 else torch.float32)
+        buf_bf, buf_mx = init.to(DEV), init.to(DEV)
+        dit.gemm(xd, wd, bias_d, buf_bf[1:M + 1, :N], epi, gate_d if epi == 3 else None)
+        _gemm(xq, xs, wq, ws, bias_d, buf_mx[1:M + 1, :N], epi, gate_d if epi == 3 else None)
+        got_bf, got_mx = buf_bf.cpu(), buf_mx.cpu()
+        assert torch.equal(got_mx, got_bf), (epi, (got_mx != got_bf).nonzero()[:8])
+        assert torch.equal(got_bf[guard], init[guard]), epi
+        if epi == 2:  # and the common bits are the right ones: an exact integer sum plus one fp32 addition
+            assert torch.equal(got_bf[1:M + 1, :N], x.float() @ w.float().T + bias)
+
+
 C2 = [(15360, 5120), (5120, 5120), (14080, 5120), (5120, 13824)]
 LONGCAT = [(12288, 4096), (4096, 4096), (22016, 4096), (4096, 11008)]
 FP32_BAR = 2e-5

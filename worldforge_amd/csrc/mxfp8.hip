@@ -5,10 +5,11 @@
 //   wf_gemm_mxfp8:    out = epi(dequant(X) . dequant(W)^T + bias) on v_mfma_scale_f32_32x32x64_f8f6f4 (2x the bf16 MFMA rate per clock),
 //                     fp32 accumulation.
 //
-// The GEMM is k_gemm_pp of gemm.hip (256-token x 256-feature tile, 8 waves, LDS-DMA double buffer, two-group ping-pong, transposed
-// epilogue) with the operand bytes halved: a K tile is 128 e4m3 elements = the same 128-byte LDS row as the 64 bf16 elements of the bf16
-// kernel, so the staging geometry, the swizzle and the DMA schedule carry over byte for byte, and each half-tile phase is ONE k-step of 64
-// (NI x NJ scaled MFMAs of twice the bf16 cycles: the same matrix-pipe time per phase as before, for twice the K).
+// The GEMM is the ping-pong kernel of gemm.hip with the operand bytes halved: a K tile is 128 e4m3 elements = the same 128-byte LDS row as
+// the 64 bf16 elements of k_gemm_pp.  From gemm_pp.h, shared with that kernel: the tile geometry (PPGeom), the XCD-aware rasteriser, the
+// wave decomposition, the LDS-DMA piece addressing and its read-phase / MFMA-gap split (PPDma), the barrier helpers and the transposed
+// epilogue (pp_epilogue, with gelu_tanh).  Written here: the scale handling, the fragment read, the scaled MFMA call and the K loop, where
+// each half-tile phase is ONE k-step of 64 (NI x NJ scaled MFMAs of twice the bf16 cycles: the same matrix-pipe time per phase, for twice the K).
 //
 // Operand maps of the scaled 32x32x64 MFMA (e4m3 A and B, 32 bytes = 8 VGPRs per lane), pinned on the device with exact-integer data and
 // distinct per-block scales (tests/test_gpu_mxfp8.py::test_gemm_layout_exact):
@@ -18,8 +19,7 @@
 //   C/D: the bf16 32x32 map (mfma.h).
 // Scales reach the lanes as one dword per fragment row and K tile (the 4 block scales of the row's 128 elements) through ordinary global
 // loads issued a K tile ahead; their wait is forced behind the tile's vmcnt(0) drain, where it costs nothing.
-#include "common.h"
-#include "mfma.h"
+#include "gemm_pp.h"
 
 using namespace wf;
 
@@ -71,8 +71,6 @@ __global__ __launch_bounds__(256) void k_mx_quant(const uint16_t* __restrict__ X
 }
 
 // ---- GEMM --------------------------------------------------------------------------------------------------------------------------------
-enum { EPI_BF16 = 0, EPI_BF16_GELU = 1, EPI_F32 = 2, EPI_RESID = 3 };
-
 struct MxArgs {
   const uint8_t* X;   // [M, ldx] e4m3
   const uint8_t* Xs;  // [M, K/32] E8M0
@@ -87,88 +85,20 @@ struct MxArgs {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
-__device__ __forceinline__ float gelu_tanh(float x) {  // the formulation of gemm.hip's gelu_tanh (same instructions, same rounding)
-  const float c = -2.0f * 0.7978845608028654f * 1.4426950408889634f, k1 = 0.044715f;
-  const float p = __builtin_fmaf(k1, x * x, 1.0f);
-  const float e = __builtin_amdgcn_exp2f((c * x) * p);
-  return x * __builtin_amdgcn_rcpf(1.0f + e);
-}
-
-constexpr int PM = 256, PKB = 128, PT = 512;  // tokens per tile, K elements (= bytes) per K tile, threads
-
-template <int NI>
-struct MxGeom {  // gemm.hip's PPGeom: the byte sizes are the same (128-byte rows)
-  static constexpr int NJ = NI == 2 ? 4 : 2;
-  static constexpr int TSPLIT = PM / (NJ * 32);
-  static constexpr int FSPLIT = 8 / TSPLIT;
-  static constexpr int PNT = FSPLIT * NI * 32;
-  static constexpr int W_TILE = PNT * PKB;
-  static constexpr int X_TILE = PM * PKB;
-  static constexpr int BUF = W_TILE + X_TILE;
-  static constexpr int NWP = PNT / 64;
-  static constexpr int NP = NWP + 4;
-  static constexpr int STG = NJ * 32 * 144;
-  static constexpr int DUMMY = 2 * BUF > 8 * STG ? 2 * BUF : 8 * STG;
-  static constexpr int LDS = DUMMY + 8 * 1024;
-};
-
-constexpr int RSPLIT = 5;  // pieces of a wave's next-tile DMA issued behind its first read phase (the rest ride in MFMA gaps): gemm.hip's value
+constexpr int PKB = PP_ROW;  // K elements (= bytes) per K tile
 
 template <int EPI, int NI>
-__global__ __launch_bounds__(PT, 2) void k_gemm_mx(MxArgs a) {
-  using G = MxGeom<NI>;
-  constexpr int NJ = G::NJ, NWP = G::NWP, NP = G::NP, W_TILE = G::W_TILE, BUF = G::BUF;
+__global__ __launch_bounds__(PP_THREADS, 2) void k_gemm_mx(MxArgs a) {
+  using G = PPGeom<NI>;
+  constexpr int NJ = G::NJ, W_TILE = G::W_TILE, BUF = G::BUF;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int smt = (a.mt + 3) >> 2, snt = (a.nt + 3) >> 2;
-  const int nsuper = smt * snt;
-  const int b = blockIdx.x;
-  const int xcd = b & 7, j = b >> 3;
-  const int gid = (j >> 4) * 8 + xcd;
-  if (gid >= nsuper) return;
-  const int within = j & 15;
-  const int tm = (gid / snt) * 4 + (within >> 2);
-  const int tn = (gid % snt) * 4 + (within & 3);
-  if (tm >= a.mt || tn >= a.nt) return;
-  const int m0 = tm * PM, n0 = tn * G::PNT;
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, hi = lane >> 5;
-  const bool groupB = wid >= 4;
-  const int wfi = NJ == 4 ? (wid & 3) : (wid >> 2);
-  const int wti = NJ == 4 ? (wid >> 2) : (wid & 3);
-  const int wf0 = wfi * NI * 32, wt0 = wti * NJ * 32;
-
-  // ---- LDS-DMA: pieces of 1 KiB (8 rows x 128 B); lane -> (row = 8*piece + lane/8, slot = lane%8) receives source chunk slot ^ ((row>>1)&7)
-  uint32_t voffW[NWP], voffX[4];
-#pragma unroll
-  for (int i = 0; i < NWP; ++i) {
-    const int row = 8 * (wid * NWP + i) + (lane >> 3), slot = lane & 7;
-    voffW[i] = (uint32_t)((size_t)min(n0 + row, a.N - 1) * a.ldw + (slot ^ ((row >> 1) & 7)) * 16);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = 8 * (wid * 4 + i) + (lane >> 3), slot = lane & 7;
-    voffX[i] = (uint32_t)((size_t)min(m0 + row, a.M - 1) * a.ldx + (slot ^ ((row >> 1) & 7)) * 16);
-  }
-  const uint32_t smem_base = __builtin_amdgcn_readfirstlane(lds_offset(smem));
+  int tm, tn;
+  if (!tile_of<PP_SUPER>(a.mt, a.nt, tm, tn)) return;
+  const int m0 = tm * PP_M, n0 = tn * G::PNT;
+  const PPWave<NI> w;
+  const int l31 = w.l31, hi = w.hi, wf0 = w.wf0, wt0 = w.wt0;
   const int nk = a.K / PKB;
-  // past the last K tile the pieces re-read tile nk-1 into a wave-private dummy region nobody reads (one code path for the MFMA phase)
-  auto piece_s = [&](int i, int kt) {
-    const bool live = kt < nk;
-    const int ks_ = live ? kt : nk - 1;
-    const uint32_t buf = smem_base + (uint32_t)((kt & 1) * BUF);
-    static_assert(G::DUMMY >= 2 * BUF && G::DUMMY >= 8 * G::STG && G::LDS >= G::DUMMY + 8 * 1024, "the dummy LDS-DMA targets overlap live LDS");
-    const uint32_t dummy = smem_base + (uint32_t)(G::DUMMY + wid * 1024);
-    if (i < NWP)
-      glds16_saddr(a.W + (size_t)ks_ * PKB, voffW[i], live ? buf + (uint32_t)((wid * NWP + i) * 1024) : dummy);
-    else
-      glds16_saddr(a.X + (size_t)ks_ * PKB, voffX[i - NWP], live ? buf + (uint32_t)(W_TILE + (wid * 4 + i - NWP) * 1024) : dummy);
-  };
-  auto dma = [&](int kt) {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) piece_s(i, kt);
-  };
+  const PPDma<NI> dma(a.W, a.X, a.N, a.M, a.ldw, a.ldx, n0, m0, nk, smem, w);
 
   // ---- block scales: per fragment row one dword per K tile (blocks 4kt .. 4kt+3 of the row) ----------------------------------------
   const int srow = a.K >> 5;  // scale bytes per row (K % 128 == 0: dword aligned)
@@ -244,11 +174,7 @@ __global__ __launch_bounds__(PT, 2) void k_gemm_mx(MxArgs a) {
 #pragma unroll
       for (int jx = 0; jx < NJ; ++jx) {
         mma(i, jx, half);
-        const int idx = i * NJ + jx;
-        if ((idx & 1) && (idx >> 1) < NP - RSPLIT) {
-          piece_s(RSPLIT + (idx >> 1), kt_next);
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        dma.gap(i * NJ + jx, kt_next);
       }
     __builtin_amdgcn_s_setprio(0);
   };
@@ -260,185 +186,61 @@ __global__ __launch_bounds__(PT, 2) void k_gemm_mx(MxArgs a) {
       for (int jx = 0; jx < NJ; ++jx) mma(i, jx, half);
     __builtin_amdgcn_s_setprio(0);
   };
-  auto bar = [&]() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  };
-  auto drain = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-  auto rphase_pieces = [&](int kt_next) {
-#pragma unroll
-    for (int i = 0; i < (RSPLIT < NP ? RSPLIT : NP); ++i) piece_s(i, kt_next);
-  };
-  static_assert(NI * NJ >= 2 * (NP - RSPLIT), "not enough MFMA gaps for the DMA pieces");
+  static_assert(NI * NJ >= 2 * (G::NP - PPDma<NI>::RS), "not enough MFMA gaps for the DMA pieces");
 
   load_scales(0);
-  dma(0);
-  drain();
+  dma.tile(0);
+  pp_drain();
   settle_scales();
-  bar();
+  pp_bar();
   // Phases as k_gemm_pp (gemm.hip): group A runs R0 M0 R1 M1 per K tile, group B the same one phase later, phase-locked by barriers
-  if (!groupB) {
+  if (!w.groupB) {
     for (int kt = 0; kt < nk; ++kt) {
       take_scales();
       read_half(kt, 0);
-      rphase_pieces(kt + 1);
+      dma.rphase(kt + 1);
       load_scales(kt + 1);
-      bar();  // 4kt+1
+      pp_bar();  // 4kt+1
       mma_half_dma(0, kt + 1);
-      bar();  // 4kt+2
+      pp_bar();  // 4kt+2
       read_half(kt, 1);
-      bar();  // 4kt+3
+      pp_bar();  // 4kt+3
       mma_half(1);
-      drain();
+      pp_drain();
       settle_scales();
-      bar();  // 4kt+4
+      pp_bar();  // 4kt+4
     }
-    bar();
+    pp_bar();
   } else {
-    if (nk > 1) dma(1);
-    bar();  // 1
+    if (nk > 1) dma.tile(1);
+    pp_bar();  // 1
     for (int kt = 0; kt < nk; ++kt) {
       take_scales();
       read_half(kt, 0);
-      if (kt > 0) rphase_pieces(kt + 1);
+      if (kt > 0) dma.rphase(kt + 1);
       load_scales(kt + 1);
-      bar();  // 4kt+2
+      pp_bar();  // 4kt+2
       mma_half(0);
-      bar();  // 4kt+3
+      pp_bar();  // 4kt+3
       read_half(kt, 1);
-      drain();
+      pp_drain();
       settle_scales();
-      bar();  // 4kt+4
+      pp_bar();  // 4kt+4
       mma_half_dma(1, kt + 2);
-      bar();  // 4kt+5
+      pp_bar();  // 4kt+5
     }
-    drain();
+    pp_drain();
   }
 
-  // ---- epilogue through LDS (k_gemm_pp's): per wave [NJ*32 tokens][128 B] passes with a 144-byte row stride, whole-row global accesses
-  {
-    constexpr int RS = 144;
-    constexpr int ROWS = NJ * 32;
-    unsigned char* stg = smem + wid * G::STG;
-    if constexpr (EPI == EPI_BF16 || EPI == EPI_BF16_GELU) {
-#pragma unroll
-      for (int i0 = 0; i0 < NI; i0 += 2) {
-        const int nti = (NI - i0) >= 2 ? 2 : 1;
-        f32x4 bq[2][4];
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) bq[ii][g] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (a.bias) {
-#pragma unroll
-          for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-              if (ii < nti) bq[ii][g] = *reinterpret_cast<const f32x4*>(a.bias + min(n0 + wf0 + (i0 + ii) * 32 + 8 * g + 4 * hi, a.N - 4));
-        }
-#pragma unroll
-        for (int jx = 0; jx < NJ; ++jx)
-#pragma unroll
-          for (int ii = 0; ii < 2; ++ii) {
-            if (ii >= nti) continue;
-            const int i = i0 + ii;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const int nl = ii * 32 + 8 * g + 4 * hi;
-              float v[4];
-#pragma unroll
-              for (int q = 0; q < 4; ++q) v[q] = acc[i][jx][4 * g + q] + bq[ii][g][q];
-              if constexpr (EPI == EPI_BF16_GELU) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = gelu_tanh(v[q]);
-              }
-              *reinterpret_cast<u32x2*>(stg + (jx * 32 + l31) * RS + nl * 2) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
-            }
-          }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const int lpr = nti * 4;
-        const int lrow = lane / lpr, lch = lane % lpr;
-#pragma unroll
-        for (int r8 = 0; r8 < ROWS * nti / 16; ++r8) {
-          const int row = r8 * (64 / lpr) + lrow;
-          const int m = m0 + wt0 + row;
-          const int n = n0 + wf0 + i0 * 32 + lch * 8;
-          const u32x4 val = *reinterpret_cast<const u32x4*>(stg + row * RS + lch * 16);
-          if (m < a.M && n < a.N) {
-            uint16_t* op = reinterpret_cast<uint16_t*>(a.out) + (size_t)m * a.ldo + n;
-            if (n + 8 <= a.N)
-              *reinterpret_cast<u32x4*>(op) = val;
-            else
-              *reinterpret_cast<u32x2*>(op) = u32x2{val[0], val[1]};
-          }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-    } else {
-      const int lrow = lane >> 3, lch = lane & 7;
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        f32x4 bq[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        if (a.bias) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const f32x4*>(a.bias + min(n0 + wf0 + i * 32 + 8 * g + 4 * hi, a.N - 4));
-        }
-#pragma unroll
-        for (int jx = 0; jx < NJ; ++jx)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int nl = 8 * g + 4 * hi;
-            f32x4 v = {acc[i][jx][4 * g + 0] + bq[g][0], acc[i][jx][4 * g + 1] + bq[g][1], acc[i][jx][4 * g + 2] + bq[g][2],
-                       acc[i][jx][4 * g + 3] + bq[g][3]};
-            *reinterpret_cast<f32x4*>(stg + (jx * 32 + l31) * RS + nl * 4) = v;
-          }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const int n = n0 + wf0 + i * 32 + lch * 4;
-        f32x4 gg = {1.f, 1.f, 1.f, 1.f};
-        if constexpr (EPI == EPI_RESID) {
-          if (a.gate) gg = *reinterpret_cast<const f32x4*>(a.gate + min(n, a.N - 4));
-        }
-        constexpr int CH = 4;
-#pragma unroll
-        for (int c0 = 0; c0 < ROWS / 8; c0 += CH) {
-          f32x4 oldv[CH];
-          if constexpr (EPI == EPI_RESID) {
-#pragma unroll
-            for (int r8 = 0; r8 < CH; ++r8) {
-              const int m = min(m0 + wt0 + (c0 + r8) * 8 + lrow, a.M - 1);
-              oldv[r8] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(a.out) + (size_t)m * a.ldo + min(n, a.N - 4));
-            }
-          }
-#pragma unroll
-          for (int r8 = 0; r8 < CH; ++r8) {
-            const int row = (c0 + r8) * 8 + lrow;
-            const int m = m0 + wt0 + row;
-            f32x4 v = *reinterpret_cast<const f32x4*>(stg + row * RS + lch * 16);
-            if (m < a.M && n < a.N) {
-              float* po = reinterpret_cast<float*>(a.out) + (size_t)m * a.ldo + n;
-              if constexpr (EPI == EPI_F32) {
-                *reinterpret_cast<f32x4*>(po) = v;
-              } else {
-                const f32x4 old = oldv[r8];
-                *reinterpret_cast<f32x4*>(po) = f32x4{old[0] + v[0] * gg[0], old[1] + v[1] * gg[1], old[2] + v[2] * gg[2], old[3] + v[3] * gg[3]};
-              }
-            }
-          }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-    }
-  }
+  pp_epilogue<EPI, NI, false>(acc, smem + w.wid * G::STG, m0 + wt0, n0 + wf0, PPEpiArgs{a.bias, a.gate, a.out, a.M, a.N, a.ldo, 1.0f});
 }
 
 template <int EPI, int NI>
 void launch_mx(MxArgs a, hipStream_t s) {
-  using G = MxGeom<NI>;
-  a.mt = ceil_div(a.M, PM);
+  using G = PPGeom<NI>;
+  a.mt = ceil_div(a.M, PP_M);
   a.nt = ceil_div(a.N, G::PNT);
-  const int nsuper = ((a.mt + 3) / 4) * ((a.nt + 3) / 4);
-  const int grid = ((nsuper + 7) / 8) * 8 * 16;
-  hipLaunchKernelGGL((k_gemm_mx<EPI, NI>), dim3(grid), dim3(PT), G::LDS, s, a);
+  hipLaunchKernelGGL((k_gemm_mx<EPI, NI>), dim3(tile_grid<PP_SUPER>(a.mt, a.nt)), dim3(PP_THREADS), G::LDS, s, a);
 }
 
 // The 256-feature tile only: the 320-feature geometry (NI = 5) needs more than the 256 VGPRs of two waves per SIMD once the scale
