@@ -193,8 +193,13 @@ int wf_lora_fold(const void* base, void* out, int N, int K, int n_adapters, cons
                  int rank2, int nsep2, float scale2, const void* U3, const void* D3, int rank3, int nsep3, float scale3, void* stream);
 
 /* flash_attention (attention.py:24-130) as used by model.py:149-154 (self) and :220-222 (cross): fused
- * softmax(Q K^T * softmax_scale) V, no mask, head_dim 128.  Q [H][Lq][128], K [H][Lkp][128] (rows >= kv_len zero),
+ * softmax(Q K^T * softmax_scale) V, no mask, head_dim 128.  Q [H][Lq][128], K [H][Lkp][128],
  * Vt [H][Lkp/64][128][64] (wf_v_transpose), O [Lq][ldo] bf16 with head h at columns h*128 (ldo % 8 == 0, O 16-byte aligned: 16-byte stores).
+ * Padding contract (all attention entry points; pinned by tests/test_gpu_attn_fp64.py): the kernel masks the scores of the keys >= kv_len
+ * of the last 64-key tile to -inf itself, so K's rows and V^T's key columns kv_len .. ceil(kv_len/64)*64 - 1 may hold ANY FINITE values
+ * (p = 0 times a finite v is 0; an inf or NaN there would leak as 0 * inf) -- the producers zero them (wf_rmsnorm_heads leaves rows
+ * L..Lout of a zeroed buffer untouched, wf_v_transpose zero-fills), but no result depends on that.  Whole tiles behind
+ * ceil(kv_len/64) (Lkp larger than needed) are never read.
  * accumulate != 0: O += result.
  * seg_len: Lkp for one contiguous K/V; with sequence parallelism K/V are the all-gathered per-rank shards [P][H][seg_len][128]
  * (seg_len % 64 == 0, Lkp = P*seg_len) and key index = seg*seg_len + row.
@@ -220,7 +225,7 @@ int wf_head_max_norm2(const void* X, int H, int L, int Lp, float* out, void* str
 size_t wf_attn_split_workspace_bytes(int H, int Lq, int nsplit);
 /* WanI2VCrossAttention (model.py:202-229) in ONE launch: O = softmax(Q K1^T s) V1 + softmax(Q K2^T s) V2 for the image context (K1, 257
  * keys) and the text context (K2, 512 keys), where the reference runs two flash_attention calls and adds (model.py:220-227).  K [H][Lk1p +
- * Lk2p][128] holds context 1 (kv_len1 valid rows of Lk1p, zero-padded to whole 64-key tiles) followed by context 2; Vt [H][(Lk1p + Lk2p) /
+ * Lk2p][128] holds context 1 (kv_len1 valid rows of Lk1p, padded to whole 64-key tiles with finite values: see the padding contract at wf_attn_fwd) followed by context 2; Vt [H][(Lk1p + Lk2p) /
  * 64][128][64] likewise (wf_v_transpose_seg).  Q is read once and O written once; context 1's normalised result is rounded to bf16 and kept
  * in registers across the seam, so the result is bit-identical to wf_attn_fwd(context 1) followed by wf_attn_fwd(context 2, accumulate). */
 int wf_attn_cross2_fwd(const void* Q, const void* K, const void* Vt, void* O, int H, int Lq, int Lk1p, int kv_len1, int Lk2p, int kv_len2,
@@ -274,7 +279,7 @@ size_t wf_rmsnorm_heads_bound_ws_floats(int L, int C);
 int wf_rmsnorm_heads_bound(const void* in, int ld, const float* weight, const float* cos_tab, const float* sin_tab, void* out, int L, int Lout,
                            int C, float eps, float out_scale, float* ws, float* max_norm2, void* stream);
 
-/* V [L, ld] bf16 (head h at columns h*128) -> Vt [H][Lp/64][128][64] bf16, keys >= L zero-filled. */
+/* V [L, ld] bf16 (head h at columns h*128) -> Vt [H][Lp/64][128][64] bf16, keys >= L zero-filled (finite is all wf_attn_fwd needs). */
 int wf_v_transpose(const void* V, int ld, void* Vt, int L, int Lp, int H, void* stream);
 /* The same into a destination whose heads are head_stride_tiles 64-key tiles apart (Vt points at the segment's first tile of head 0): the
  * two contexts of wf_attn_cross2_fwd share one buffer. */

@@ -5,7 +5,7 @@
 // This is the roofline-graded kernel: 4*Lq*Lk*128 flop per head, MFMA-bound.
 //
 // Layouts (produced by wf_qk_norm_rope / wf_v_transpose in dit_ops.hip):
-//   Q  [H][Lq ][128] bf16     K [H][Lkp][128] bf16 (rows >= kv_len are zero)
+//   Q  [H][Lq ][128] bf16     K [H][Lkp][128] bf16 (rows >= kv_len: any finite value, their scores are masked)
 //   Vt [H][Lkp/64][128][64] bf16  -- V transposed and blocked by 64 keys, so that a KV tile is 16 KiB contiguous and the
 //                                    P.V MFMA reads its A operand (d x keys) with plain 16-byte LDS reads, no transpose
 //   O  [Lq][H*128] bf16 (token-major: the A operand of the o-projection GEMM)
