@@ -284,6 +284,14 @@ int wf_v_transpose(const void* V, int ld, void* Vt, int L, int Lp, int H, void* 
 /* The same into a destination whose heads are head_stride_tiles 64-key tiles apart (Vt points at the segment's first tile of head 0): the
  * two contexts of wf_attn_cross2_fwd share one buffer. */
 int wf_v_transpose_seg(const void* V, int ld, void* Vt, int L, int Lp, int H, int head_stride_tiles, void* stream);
+/* APPEND at an arbitrary key offset (csrc/longcat_ops.hip; LongCat video continuation, attention.py:149-181: the condition frames' keys
+ * [0, k0) of K / V^T stay resident across the denoising steps and each step's noise keys follow at k0 = condition tokens, in general
+ * not a multiple of 64): V [L, ld] bf16 (head h at columns h*128) -> keys [k0, k0 + L) of Vt [H][Lp/64][128][64].  Keys < k0 keep their
+ * bits, those sharing the first touched tile included (never read, never written: per-key stores where k0 cuts an 8-key chunk); keys
+ * k0 + L .. end of the last touched tile are zero-filled; later tiles are not touched.  k0 = 0: the bits of wf_v_transpose in every tile
+ * below ceil(L / 64).  WF_EINVAL before any device work unless k0 >= 0, L > 0, k0 + L <= Lp, Lp % 64 == 0, ld % 8 == 0, ld >= H * 128,
+ * non-null 16-byte aligned pointers. */
+int wf_v_transpose_at(const void* V, int ld, void* Vt, int k0, int L, int Lp, int H, void* stream);
 
 /* model.py:534-537 patch embedding as a GEMM: x bf16 [Cin,T,Hh,Ww] -> tokens bf16 [T*(Hh/2)*(Ww/2), Cin*4] (k = c*4+ph*2+pw). */
 int wf_patchify(const void* x, void* tokens, int Cin, int T, int Hh, int Ww, void* stream);

@@ -207,6 +207,49 @@ __global__ void k_gather_rows(const uint16_t* __restrict__ in, int64_t ld_in, co
   }
 }
 
+// V rows [0, L) -> keys [k0, k0 + L) of the blocked V^T [H][tiles_per_head][128][64]: the step's noise keys behind the resident
+// condition keys of a video-continuation cache (LCA:149-181; k0 = condition tokens, in general not a multiple of 64).  One workgroup
+// per TOUCHED 64-key tile and head, staged through LDS exactly as k_vt of dit_ops.hip (16-byte loads of V's rows, 16-byte stores of 8
+// keys of one channel); a source row below 0 or at / behind L reads as zero, so the keys behind k0 + L of the last tile are
+// zero-filled.  In the first tile the 8-key chunks wholly below k0 are skipped and the ONE chunk per channel that k0 cuts is written
+// key by key (2-byte stores under a per-lane predicate): no byte of the resident prefix is read or written, so nothing can race with
+// whoever owns it.
+__global__ __launch_bounds__(256) void k_vt_at(const uint16_t* __restrict__ V, int ld, uint16_t* __restrict__ Vt, int k0, int L,
+                                               int tiles_per_head) {
+  __shared__ uint16_t tile[64][136];
+  const int kt = k0 / 64 + blockIdx.x, head = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int first = k0 - kt * 64;  // keys [0, first) of this tile are resident (first <= 0 in every tile but the first)
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int id = tid + 256 * i;
+    const int r = id >> 4, c = id & 15;
+    const int row = r - first;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (row >= 0 && row < L) v = *reinterpret_cast<const u32x4*>(V + (size_t)row * ld + head * 128 + c * 8);
+    *reinterpret_cast<u32x4*>(&tile[r][c * 8]) = v;
+  }
+  __syncthreads();
+  uint16_t* dst = Vt + ((size_t)head * tiles_per_head + kt) * (128 * 64);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int id = tid + 256 * i;
+    const int d = id >> 3, c = id & 7;
+    if (c * 8 + 8 <= first) continue;  // resident keys only
+    if (c * 8 >= first) {
+      uint32_t p[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) p[k] = (uint32_t)tile[c * 8 + 2 * k][d] | ((uint32_t)tile[c * 8 + 2 * k + 1][d] << 16);
+      u32x4 pk = {p[0], p[1], p[2], p[3]};
+      *reinterpret_cast<u32x4*>(dst + d * 64 + c * 8) = pk;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c * 8 + k >= first) dst[d * 64 + c * 8 + k] = tile[c * 8 + k][d];
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------
 // Block selection of the sparse attention (bsa_interface.py:211-224): top n_sel of n_k block scores per query block, turned straight
 // into the per-workgroup lists wf_attn_bsa_fwd walks (worldforge_amd/bsa.py group_lists: union of the g query blocks of a workgroup in
@@ -514,5 +557,17 @@ extern "C" int wf_lc_swiglu(const void* in, int64_t ld, void* out, int L, int Hd
   hipLaunchKernelGGL(k_lc_swiglu, dim3(grid_for(n8, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)in, ld,
                      (uint16_t*)out, Hd, n8);
   WF_LAUNCH_CHECK("wf_lc_swiglu");
+  return WF_OK;
+}
+
+extern "C" int wf_v_transpose_at(const void* V, int ld, void* Vt, int k0, int L, int Lp, int H, void* stream) {
+  WF_CHECK_ARG(V && Vt, "wf_v_transpose_at: null pointer");
+  WF_CHECK_ARG(k0 >= 0 && L > 0 && H > 0 && Lp % 64 == 0 && (int64_t)k0 + L <= Lp,
+               "wf_v_transpose_at: need k0 >= 0, L > 0, k0 + L <= Lp, Lp %% 64 == 0 (k0=%d L=%d Lp=%d)", k0, L, Lp);
+  WF_CHECK_ARG(ld % 8 == 0 && (int64_t)ld >= (int64_t)H * 128, "wf_v_transpose_at: ld=%d must be a multiple of 8 and >= H * 128", ld);
+  WF_CHECK_ARG((((uintptr_t)V | (uintptr_t)Vt) & 15) == 0, "wf_v_transpose_at: 16-byte alignment");
+  const int tiles = (k0 + L - 1) / 64 - k0 / 64 + 1;
+  hipLaunchKernelGGL(k_vt_at, dim3(tiles, H), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)V, ld, (uint16_t*)Vt, k0, L, Lp / 64);
+  WF_LAUNCH_CHECK("wf_v_transpose_at");
   return WF_OK;
 }

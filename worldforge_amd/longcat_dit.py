@@ -16,7 +16,14 @@ Runtime LoRA (LCD:189-270): `load_lora` / `enable_loras` / `disable_all_loras` k
 weights on the GPU (csrc/lora.hip: effective = bf16(base + sum of the active adapters' scaled products), one rounding, from an untouched
 base copy), so the forward still runs on plain bf16 matrices and a LoRA costs nothing per step; `fold_lora` is the host-side state-dict
 route (a fold before load_state_dict, not undoable).  Block-sparse attention (LCA:57-66; `enable_bsa`, bsa.py)
-and sequence parallelism (`comm`, parallel.py) are built.  Not covered here: KV-cache continuation (LCA:147-181).
+and sequence parallelism (`comm`, parallel.py) are built.
+
+Video continuation (LCA:147-181, PIPE:336-348): `cache_condition` runs the condition frames' stream once (timestep 0, no caption, no
+cross-attention: it depends on neither the noise tokens, the prompt nor the step) and keeps every block's K / V^T / norm bound resident
+in the attention kernel's layout (LongCatCondCache); `forward_tokens_cached` / `forward_cached` then run the noise frames only, appending
+their keys behind the cached ones (wf_lc_norm_heads at a row offset, wf_v_transpose_at) in front of the one noise-query attention launch
+of the uncached forward.  A cache is bound to the weights it was built with (weights version, adapters, linear_precision) and to its
+latent size.  Not built: continuation under sequence parallelism or block-sparse attention, CPU offload of the cache.
 """
 from __future__ import annotations
 
@@ -126,6 +133,23 @@ _LORA_H = "___lorahyphen___"
 
 
 @dataclass(eq=False)
+class LongCatCondCache:
+    """The condition frames' self-attention keys / values of every block (LCA:149-181 `kv_cache_dict`), resident on the GPU in the
+    layout wf_attn_fwd reads, built by LongCatVideoTransformer3DModel.cache_condition.  K is normalised AND rotated: a frame's RoPE rows
+    do not depend on how many frames follow (rope_tables), so the rotation of LCA:168-172 is done once."""
+    k: torch.Tensor        # bf16 [depth, H, pad64(nc), 128], rows nc.. zero
+    vt: torch.Tensor       # bf16 [depth, H, pad64(nc) / 64, 128, 64], keys nc.. zero
+    kmax2: torch.Tensor    # f32 [depth, H]: max |k row|^2 per head over the nc cached rows (wf_head_max_norm2)
+    ncl: int               # condition latent frames
+    nc: int                # condition tokens = ncl * tokens per frame
+    latent_hw: Tuple[int, int]
+    owner: object          # the model's token, and what its weights were when the cache was built:
+    wver: int
+    loras: Tuple[str, ...]
+    linear_precision: str
+
+
+@dataclass(eq=False)
 class LoRAPart:
     """One wrapped Linear of one adapter, placed in this model's fused storage: rows [row0, row0 + U.shape[0]) of matrix `wkey`."""
     wkey: str
@@ -162,6 +186,8 @@ class LongCatVideoTransformer3DModel:
         self.w: Dict[str, torch.Tensor] = {}
         self._ws = {}
         self._rope = {}
+        self._token = object()  # what a LongCatCondCache names its model by
+        self.last_kmax2 = self.last_vc_keys = None  # forward_tokens_cached: the last block's key norm bound and (working K, key count)
         # block-sparse self-attention of the 720p refine pass (LCA:57-66, LCD:270-276); bsa_params as in the reference's config:
         # sparsity, chunk_3d_shape_q, chunk_3d_shape_k (cdf_threshold is not built)
         self._bsa = bool(enable_bsa)
@@ -189,7 +215,10 @@ class LongCatVideoTransformer3DModel:
 
     def weights_changed(self):
         """Call after editing (base) weight tensors IN PLACE: with adapters active the effective weights are folded again from the
-        base, then the MX-fp8 copies of linear_precision="mxfp8" are re-derived (none in bf16)."""
+        base, then the MX-fp8 copies of linear_precision="mxfp8" are re-derived (none in bf16).  Every path that changes the weights
+        the forward runs on ends here (the `w` setter, load_state_dict, the LoRA switches): the version counter makes a
+        LongCatCondCache built before it unusable."""
+        self._wver = getattr(self, "_wver", 0) + 1
         try:
             self._w = self._fold_active() if self.active_loras else self._base
         except Exception:  # a switch that cannot be made leaves the base model, not half-folded buffers
@@ -436,18 +465,26 @@ class LongCatVideoTransformer3DModel:
         call("wf_lc_gate_residual", x.data_ptr(), y.data_ptr(), y.stride(0), gate.data_ptr() if gate is not None else None, gate_ld,
              rows_per_group, row0, gidx.data_ptr() if gidx is not None and gate is not None else None, L, C, ops.stream())
 
-    def _heads(self, src, col0, weight, cos, sin, out, r0, r1, out_scale=1.0):
-        """Rows [r0, r1) of columns [col0, col0 + C) of src -> out [H, Lout, 128] rows [0, r1 - r0)."""
+    def _heads(self, src, col0, weight, cos, sin, out, r0, r1, out_scale=1.0, lout: Optional[int] = None):
+        """Rows [r0, r1) of columns [col0, col0 + C) of src -> out [H, Lout, 128] rows [0, r1 - r0).  lout: rows between two heads of
+        the destination when `out` is a row range of a larger [H, lout, 128] buffer (the noise keys behind the cached condition keys)."""
         if r1 <= r0:
             return
         view = src[r0:r1, col0:col0 + self.cfg.hidden_size]
         call("wf_lc_norm_heads", view.data_ptr(), src.stride(0), weight.data_ptr(),
              cos[r0:r1].data_ptr() if cos is not None else None, sin[r0:r1].data_ptr() if sin is not None else None,
-             out.data_ptr(), r1 - r0, out.shape[1], self.cfg.num_heads, float(self.cfg.eps), float(out_scale), ops.stream())
+             out.data_ptr(), r1 - r0, out.shape[1] if lout is None else lout, self.cfg.num_heads, float(self.cfg.eps), float(out_scale),
+             ops.stream())
 
     def _vt(self, src, col0, out, L):
         view = src[:, col0:col0 + self.cfg.hidden_size]
         call("wf_v_transpose", view.data_ptr(), src.stride(0), out.data_ptr(), L, out.shape[1] * 64, self.cfg.num_heads, ops.stream())
+
+    def _vt_at(self, src, col0, out, k0, L):
+        """The same behind k0 resident keys of out [H, Lp / 64, 128, 64] (wf_v_transpose_at)."""
+        view = src[:, col0:col0 + self.cfg.hidden_size]
+        call("wf_v_transpose_at", view.data_ptr(), src.stride(0), out.data_ptr(), k0, L, out.shape[1] * 64, self.cfg.num_heads,
+             ops.stream())
 
     # ------------------------------------------------------------------------------------------------------------
     # Exchange of a forward WITHOUT a lock-step partner (the distilled schedule has no CFG; see dit.WanTransformer3DModel for the modes);
@@ -494,7 +531,7 @@ class LongCatVideoTransformer3DModel:
                     live.remove(gen)
         return oa[0], ob[0]
 
-    def _forward_steps(self, x_in, timesteps, caption, caption_mask, num_cond_latents, tag, result, mode="gather"):
+    def _forward_steps(self, x_in, timesteps, caption, caption_mask, num_cond_latents, tag, result, mode="gather", vc=None):
         """Generator over one forward: yields once per dense block, right after that block's K / V^T exchange has been launched (where
         another forward can usefully take over the compute stream); `tag` separates the workspaces of concurrent forwards; the velocity
         lands in result[0].
@@ -503,7 +540,13 @@ class LongCatVideoTransformer3DModel:
         work on its shard, K and blocked V^T shards are exchanged once per block (parallel.KVExchange) and consumed in place by the
         attention kernel (segment addressing), the 64-column output rows are gathered at the end.  The condition / noise split of
         LCA:123-138 is by GLOBAL token index: a rank's rows below the first frame boundary are condition queries (keys < nc), the rest
-        noise queries."""
+        noise queries.
+
+        vc (video continuation, single GPU, dense attention) = ("build", cache): x_in holds condition frames only -- the stream of
+        LCA:127-131 / PIPE:336-348 (no caption, no cross-attention, no final layer), whose K / V^T / norm bound of every block are
+        written straight into `cache`; nothing lands in result.  ("use", cache): x_in holds the noise frames only; the cache's keys are
+        copied to the front of a working K / V^T pair, this step's keys are appended behind them, and everything else runs on the
+        noise rows."""
         cfg, W, dev = self.cfg, self._wl, self.device
         bf, f32 = torch.bfloat16, torch.float32
         Cin, T, Hh, Ww = x_in.shape
@@ -511,11 +554,15 @@ class LongCatVideoTransformer3DModel:
         C, H, Hd, Ct = cfg.hidden_size, cfg.num_heads, cfg.ffn_hidden, cfg.adaln_tembed_dim
         h2, w2 = Hh // 2, Ww // 2
         tpf = h2 * w2
-        L, Lp = T * tpf, _pad64(T * tpf)
-        nc = int(num_cond_latents or 0) * tpf
-        assert 0 <= nc < L
+        build = vc is not None and vc[0] == "build"
+        cache = vc[1] if vc is not None else None
+        # kc / fc: the cached condition keys / frames IN FRONT of this forward's rows (0 unless vc = "use")
+        kc, fc = (cache.nc, cache.ncl) if vc is not None and not build else (0, 0)
+        L, Lp = T * tpf, _pad64(kc + T * tpf)
+        nc = L if build else int(num_cond_latents or 0) * tpf
+        assert 0 <= nc < L or build
         scale = 1.0 / math.sqrt(128.0)
-        cos, sin = self._rope_tables(T, h2, w2)
+        cos, sin = self._rope_tables(fc + T, h2, w2)
         _buf = lambda name, shape, dtype, zero=False: self._buf(name + tag, shape, dtype, zero)  # noqa: E731
         comm = self.comm
         use_bsa = self._bsa and T > 1  # LCA:57: "bsa will not be used in image training / sampling"
@@ -556,7 +603,7 @@ class LongCatVideoTransformer3DModel:
         else:
             plan, lo, Lr, Sp = None, 0, L, Lp
         ncr = min(max(nc - lo, 0), Lr)  # this rank's condition rows
-        cos, sin = cos[lo:lo + Lr], sin[lo:lo + Lr]
+        cos, sin = cos[kc + lo:kc + lo + Lr], sin[kc + lo:kc + lo + Lr]
 
         # ---- embeddings ----
         tok = _buf("tok", (L, Cin * 4), bf)
@@ -567,7 +614,7 @@ class LongCatVideoTransformer3DModel:
                  ops.stream())
             tok = tokb
         tok = tok[lo:lo + Lr]
-        L_all, nc_all = L, nc
+        L_all, nc_all = kc + L, nc
         L, nc = Lr, ncr  # from here on L / nc are this rank's row counts; L_all / nc_all the key counts
         x = _buf("x", (L, C), bf)
         gemm(tok, W["patch.w"], W["patch.b"], x, EPI_BF16)  # LCB:112 (Conv3d with kernel = stride = patch)
@@ -576,21 +623,23 @@ class LongCatVideoTransformer3DModel:
         t = self._gemm_f32(self._act(t0, f32, 0), W["t_embedder.mlp.2.w"], W["t_embedder.mlp.2.b"], _buf("t", (T, Ct), f32))
         st = self._act(t, f32, 0)  # SiLU(t), shared by every adaLN_modulation (LCD:40-43, LCB:156)
         ada = self._gemm_f32(st, W["ada.w"], W["ada.b"], _buf("ada", (T, W["ada.w"].shape[0]), f32))   # (all stored blocks: a run on the first cfg.depth blocks only reads its own columns)
-        fmod = self._gemm_f32(st, W["final_layer.adaLN_modulation.1.w"], W["final_layer.adaLN_modulation.1.b"], _buf("fmod", (T, 2 * C), f32))
-        # caption: Linear -> GELU(tanh) -> Linear (LCB:225-228), valid tokens only (LCD:319-325)
-        cap = caption
-        if caption_mask is not None:
-            keep = torch.as_tensor(caption_mask).reshape(-1).to("cpu") != 0
-            if not cfg.text_tokens_zero_pad:
-                cap = caption[keep.to(caption.device)]
-        n_txt = cap.shape[0]
-        assert n_txt > 0, "empty caption"
-        yh = _buf("yh", (n_txt, C), bf)
-        gemm(cap.contiguous(), W["y_embedder.y_proj.0.w"], W["y_embedder.y_proj.0.b"], yh, EPI_BF16_GELU)
-        y = _buf("y", (n_txt, C), bf)
-        gemm(yh, W["y_embedder.y_proj.2.w"], W["y_embedder.y_proj.2.b"], y, EPI_BF16)
-        if caption_mask is not None and cfg.text_tokens_zero_pad:
-            y[(~keep).to(dev)] = 0  # LCD:315-317
+        y, n_txt = None, 0
+        if not build:
+            fmod = self._gemm_f32(st, W["final_layer.adaLN_modulation.1.w"], W["final_layer.adaLN_modulation.1.b"], _buf("fmod", (T, 2 * C), f32))
+            # caption: Linear -> GELU(tanh) -> Linear (LCB:225-228), valid tokens only (LCD:319-325)
+            cap = caption
+            if caption_mask is not None:
+                keep = torch.as_tensor(caption_mask).reshape(-1).to("cpu") != 0
+                if not cfg.text_tokens_zero_pad:
+                    cap = caption[keep.to(caption.device)]
+            n_txt = cap.shape[0]
+            assert n_txt > 0, "empty caption"
+            yh = _buf("yh", (n_txt, C), bf)
+            gemm(cap.contiguous(), W["y_embedder.y_proj.0.w"], W["y_embedder.y_proj.0.b"], yh, EPI_BF16_GELU)
+            y = _buf("y", (n_txt, C), bf)
+            gemm(yh, W["y_embedder.y_proj.2.w"], W["y_embedder.y_proj.2.b"], y, EPI_BF16)
+            if caption_mask is not None and cfg.text_tokens_zero_pad:
+                y[(~keep).to(dev)] = 0  # LCD:315-317
         Ltp = _pad64(n_txt)
 
         hbuf = _buf("h", (L, C), bf)
@@ -611,6 +660,13 @@ class LongCatVideoTransformer3DModel:
             if not prescale or comm.world == 1:
                 mode = "gather"   # part launches are built for the pre-scaled-Q form
             ex = self._exchange(tag, H, Sp, mode, int(self.exchange_chunks))
+        elif vc is not None:
+            # continuation: the working pair of ("use") has names of its own -- the uncached forward scans its zero-initialised K up to
+            # the pad for the norm bound and must never find another forward's rows there; ("build") writes the cache's own tensors
+            if not build:
+                kh = _buf("kh_vc", (H, Sp, 128), bf, zero=True)
+                vt = _buf("vt_vc", (H, Sp // 64, 128, 64), bf, zero=True)
+                km = _buf("kmax2_vc", (H,), f32) if use_bounds else None
         else:
             kh = _buf("kh", (H, Sp, 128), bf, zero=True)
             vt = _buf("vt", (H, Sp // 64, 128, 64), bf)
@@ -703,11 +759,28 @@ class LongCatVideoTransformer3DModel:
             else:
                 self._heads(qkv, 0, W[p + "attn.q_norm"], cos, sin, qh_c, 0, nc, out_scale=q_scale)
                 self._heads(qkv, 0, W[p + "attn.q_norm"], cos, sin, qh_n, nc, L, out_scale=q_scale)
-                if ex is None:
+                if vc is not None and not build:
+                    # LCA:163-172 with the rotation already in the cache: cached keys [0, kc), this step's keys behind them
+                    ct = cache.vt.shape[2]
+                    kh[:, :kc].copy_(cache.k[i, :, :kc])
+                    vt[:, :ct].copy_(cache.vt[i])
+                    self._heads(qkv, C, W[p + "attn.k_norm"], cos, sin, kh[:, kc:], 0, L, lout=Sp)
+                    self._vt_at(qkv, 2 * C, vt, kc, L)
+                    if use_bounds:
+                        # the un-tracked softmax body is only safe under a bound over ALL kc + L keys: the cached rows' maximum, raised
+                        # by the new rows' (wf_head_max_norm2 only ever raises `out`; its row window is offset to key kc)
+                        km.copy_(cache.kmax2[i])
+                        call("wf_head_max_norm2", kh[:, kc:].data_ptr(), H, L, Sp, km.data_ptr(), ops.stream())
+                    self.last_kmax2, self.last_vc_keys = km, (kh, kc + L)
+                elif ex is None:
+                    if build:
+                        kh, vt, km = cache.k[i], cache.vt[i], cache.kmax2[i]
                     self._heads(qkv, C, W[p + "attn.k_norm"], cos, sin, kh, 0, L)
                     self._vt(qkv, 2 * C, vt, L)
-                    if use_bounds:  # zero rows past L do not raise a maximum: the whole (padded) shard is scanned
+                    if use_bounds or build:  # zero rows past L do not raise a maximum: the whole (padded) shard is scanned
                         head_max_norm2(kh, Sp, km)
+                    if build and i == cfg.depth - 1:
+                        return  # the last block's keys are in the cache: nothing reads the condition stream behind them
                 else:
                     for g in range(ex.G):
                         r0, r1 = ex.chunk_rows(g, L)
@@ -766,6 +839,7 @@ class LongCatVideoTransformer3DModel:
             self._resid(x, ys, gate_mlp, ald, tpf, row0=lo, gidx=gidx)
 
         # ---- final layer (LCB:159-168) + unpatchify (LCD:371-392) ----
+        assert not build
         self._ln(x, fmod[:, C:], fmod[:, :C], fmod.stride(0), tpf, True, hbuf, row0=lo, gidx=gidx)
         yo = _buf("yo", (L, 4 * cfg.out_channels), f32)
         gemm(hbuf, W["final_layer.linear.w"], W["final_layer.linear.b"], yo, EPI_F32)
@@ -780,11 +854,8 @@ class LongCatVideoTransformer3DModel:
         call("wf_unpatchify", yo.data_ptr(), out.data_ptr(), cfg.out_channels, T, Hh, Ww, ops.stream())
         result[0] = out
 
-    def __call__(self, hidden_states: torch.Tensor, timestep: torch.Tensor, encoder_hidden_states: torch.Tensor,
-                 encoder_attention_mask: Optional[torch.Tensor] = None, num_cond_latents: int = 0, return_kv: bool = False,
-                 kv_cache_dict=None, skip_crs_attn: bool = False, offload_kv_cache: bool = False) -> torch.Tensor:
-        if return_kv or kv_cache_dict or skip_crs_attn:
-            raise NotImplementedError("KV-cache continuation (LCA:147-181) is not built; the guided i2v path does not use it")
+    def _batch_samples(self, hidden_states, timestep, encoder_hidden_states, encoder_attention_mask):
+        """The diffusers-style batch -> one (x_in, timesteps, caption, caption_mask) of forward_tokens per sample."""
         B, _, T, _, _ = hidden_states.shape
         ts = torch.as_tensor(timestep)
         if ts.dim() == 1:
@@ -801,6 +872,75 @@ class LongCatVideoTransformer3DModel:
                 x = ops.cast(x.contiguous(), torch.bfloat16)
             mask = encoder_attention_mask[b] if encoder_attention_mask is not None else None
             samples.append((x.contiguous(), ts[b].tolist(), cap[b].to(torch.bfloat16).contiguous(), mask))
+        return samples
+
+    # ---- video continuation on a resident condition cache (LCA:147-181, PIPE:336-348) --------------------------------------------
+    def _vc_guard(self):
+        if self.comm is not None:
+            raise NotImplementedError("video continuation under sequence parallelism (`comm`) is not built")
+        if self._bsa:
+            raise NotImplementedError("video continuation with block-sparse attention is not built (the reference's refine pass does "
+                                      "not use the KV cache: disable_bsa() first)")
+
+    def cache_condition(self, cond_latents: torch.Tensor) -> LongCatCondCache:
+        """PIPE:336-348 (`_cache_clean_latents`: timestep 0, skip_crs_attn, return_kv).  cond_latents [16, ncl, Hh, Ww] (normalised
+        condition latents, bf16 or cast to it) -> the cache of their keys / values in every block.  Stays on the GPU
+        (`offload_kv_cache` has no counterpart); shared by the samples of a CFG batch (LCA:163-165)."""
+        self._vc_guard()
+        cfg, dev = self.cfg, self.device
+        x = cond_latents if cond_latents.dtype == torch.bfloat16 else ops.cast(cond_latents.contiguous(), torch.bfloat16)
+        x = x.to(dev).contiguous()
+        _, ncl, Hh, Ww = x.shape
+        nc = ncl * (Hh // 2) * (Ww // 2)
+        assert nc > 0
+        H, ncp = cfg.num_heads, _pad64(nc)
+        cache = LongCatCondCache(
+            k=torch.zeros((cfg.depth, H, ncp, 128), dtype=torch.bfloat16, device=dev),
+            vt=torch.empty((cfg.depth, H, ncp // 64, 128, 64), dtype=torch.bfloat16, device=dev),
+            kmax2=torch.zeros((cfg.depth, H), dtype=torch.float32, device=dev),
+            ncl=ncl, nc=nc, latent_hw=(Hh, Ww), owner=self._token, wver=self._wver, loras=tuple(self.active_loras),
+            linear_precision=self.linear_precision)
+        for _ in self._forward_steps(x, [0.0] * ncl, None, None, ncl, "", [None], "gather", vc=("build", cache)):
+            pass
+        return cache
+
+    def _check_cache(self, cache: LongCatCondCache, latent_hw):
+        self._vc_guard()
+        if cache.owner is not self._token or cache.wver != self._wver or cache.loras != tuple(self.active_loras) \
+                or cache.linear_precision != self.linear_precision:
+            raise ValueError("the condition cache was built with other weights (another model, a weight load / weights_changed(), a LoRA "
+                             "switch or another linear_precision since): build it again with cache_condition()")
+        if tuple(latent_hw) != tuple(cache.latent_hw):
+            raise ValueError(f"the condition cache holds {cache.latent_hw[0]} x {cache.latent_hw[1]} latent frames, the input is "
+                             f"{latent_hw[0]} x {latent_hw[1]}")
+
+    def forward_tokens_cached(self, x_in: torch.Tensor, timesteps, caption: torch.Tensor, caption_mask: Optional[torch.Tensor],
+                              cache: LongCatCondCache) -> torch.Tensor:
+        """One sample of LCA:149-181 `forward_with_kv_cache`: x_in [16, T, Hh, Ww] bf16 holds the NOISE frames only (frames cache.ncl ..
+        of the video), timesteps their T host floats -> velocity [16, T, Hh, Ww] fp32.  The mathematical value of the noise frames of
+        forward_tokens(concatenated latents, condition timesteps 0, num_cond_latents = cache.ncl): the condition stream does not depend
+        on the noise tokens, the caption or the step."""
+        self._check_cache(cache, x_in.shape[-2:])
+        out = [None]
+        for _ in self._forward_steps(x_in, timesteps, caption, caption_mask, 0, "", out, "gather", vc=("use", cache)):
+            pass
+        return out[0]
+
+    def forward_cached(self, hidden_states: torch.Tensor, timestep: torch.Tensor, encoder_hidden_states: torch.Tensor,
+                       encoder_attention_mask: Optional[torch.Tensor], cache: LongCatCondCache) -> torch.Tensor:
+        """The batch form (the call of PIPE:1218-1225 with kv_cache_dict): hidden_states [B, 16, T, Hh, Ww] noise frames, the
+        conversions of __call__; the samples run one after the other on the one cache.  -> fp32 [B, 16, T, Hh, Ww]."""
+        samples = self._batch_samples(hidden_states, timestep, encoder_hidden_states, encoder_attention_mask)
+        return torch.stack([self.forward_tokens_cached(*smp, cache) for smp in samples])
+
+    def __call__(self, hidden_states: torch.Tensor, timestep: torch.Tensor, encoder_hidden_states: torch.Tensor,
+                 encoder_attention_mask: Optional[torch.Tensor] = None, num_cond_latents: int = 0, return_kv: bool = False,
+                 kv_cache_dict=None, skip_crs_attn: bool = False, offload_kv_cache: bool = False) -> torch.Tensor:
+        if return_kv or kv_cache_dict or skip_crs_attn:
+            raise NotImplementedError("the reference's kv_cache_dict protocol (LCA:147-181) is not spoken by __call__: build the condition "
+                                      "cache with cache_condition() and run forward_cached() / forward_tokens_cached()")
+        samples = self._batch_samples(hidden_states, timestep, encoder_hidden_states, encoder_attention_mask)
+        B = len(samples)
         if B == 2 and self.comm is not None and self.comm.world > 1 and self.pair_lockstep:
             # the CFG batch (pipeline_longcat_video.py:857-866): two forwards in lock-step, each exchange hidden under the other's block
             return torch.stack(self.forward_tokens_pair(samples[0], samples[1], num_cond_latents))

@@ -1,6 +1,7 @@
 """The LongCat-Video guided image-to-video sampler (IRR re-noising, FLF gate, DSG auto-guidance, CFG-zero), HIP-backed.
 
 Host-side mirror of `LongCatVideoPipeline.generate_i2v` (PIPE = longcat_for_worldforge/longcat_video/pipeline_longcat_video.py:619-1006)
+of `generate_vc` (PIPE:1010-1267, video continuation from the last frames of a video, on the DiT's resident condition KV cache)
 and of `generate_refine` (PIPE:1271-1511, the 720p refine pass):
 same sampling knobs, same control flow (PIPE:823-994), same RNG draw order (CPU generator: noise latents PIPE:256, the posterior sample
 of the conditioning frame PIPE:278, the re-noise draws PIPE:925), same dtype hand-offs (fp32 latents, DiT input / timesteps in the
@@ -83,6 +84,128 @@ class LongCatVideoPipeline:
         latents[:, :, :1] = ops.latent_norm(cond, self.vae.config.latents_mean, self.vae.config.latents_std)
         return latents
 
+    # ---- PIPE:214-286 with a conditioning video -----------------------------------------------------------------------------
+    def prepare_latents_video(self, video: torch.Tensor, batch_size: int, num_channels_latents: int, height: int, width: int,
+                              num_frames: int, num_cond_frames: int, dtype: torch.dtype, generator=None,
+                              latents: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """video [B, 3, F, H, W] in [-1, 1]: its LAST num_cond_frames frames are encoded (PIPE:272), sampled, normalised in `dtype`
+        (PIPE:280-281: generate_vc holds its latents in the DiT dtype) and written over the first latent frames of the noise."""
+        T = (num_frames - 1) // self.vae_scale_factor_temporal + 1
+        shape = (batch_size, num_channels_latents, T, height // self.vae_scale_factor_spatial, width // self.vae_scale_factor_spatial)
+        latents = (self._randn(shape, generator) if latents is None else latents.to(self.device)).to(dtype)  # PIPE:234, 252
+        cond = []
+        for i in range(batch_size):
+            enc_in = video[i][:, -num_cond_frames:].unsqueeze(0)
+            assert enc_in.shape[2] == num_cond_frames, "the video has fewer frames than num_cond_frames"  # PIPE:276
+            cond.append(self.vae.encode(enc_in).latent_dist.sample(generator))
+        cond = torch.cat(cond, dim=0).to(self.device, dtype)
+        mean = torch.tensor(self.vae.config.latents_mean).view(1, -1, 1, 1, 1).to(self.device, dtype)  # PIPE:385-394 in `dtype`
+        istd = 1.0 / torch.tensor(self.vae.config.latents_std).view(1, -1, 1, 1, 1).to(self.device, dtype)
+        ncl = 1 + (num_cond_frames - 1) // self.vae_scale_factor_temporal
+        latents[:, :, :ncl] = (cond - mean) * istd
+        return latents
+
+    def _preprocess_video(self, video, height, width) -> torch.Tensor:
+        """diffusers VideoProcessor.preprocess_video without the resize: uint8 frames [F, H, W, 3] (tensor / array / list of arrays, what
+        this pipeline's own output is times 255) or a float video [3, F, H, W] / [1, 3, F, H, W] in [0, 1] -> [1, 3, F, H, W] fp32 in [-1, 1]."""
+        v = torch.as_tensor(np.array(video)) if not isinstance(video, torch.Tensor) else video
+        if v.dtype == torch.uint8:
+            if v.dim() != 4 or v.shape[-1] != 3:
+                raise ValueError("uint8 video must be frames [F, H, W, 3]")
+            v = v.permute(3, 0, 1, 2).to(torch.float32) / 255.0
+        v = (v if v.dim() == 5 else v.unsqueeze(0)).to(torch.float32)
+        if v.dim() != 5 or v.shape[1] != 3 or tuple(v.shape[-2:]) != (height, width):
+            raise ValueError(f"video is {tuple(v.shape)}, expected [1, 3, F, {height}, {width}] (resizing to the bucket belongs to the front-end)")
+        return 2.0 * v - 1.0
+
+    # ---- PIPE:1010-1267 ---------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def generate_vc(self, video, height: int, width: int, prompt_embeds: torch.Tensor, prompt_attention_mask: torch.Tensor,
+                    negative_prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_attention_mask: Optional[torch.Tensor] = None,
+                    num_frames: int = 93, num_cond_frames: int = 13, num_inference_steps: int = 50, use_distill: bool = False,
+                    guidance_scale: float = 4.0, generator=None, latents: Optional[torch.Tensor] = None, output_type: str = "np",
+                    use_kv_cache: bool = True, offload_kv_cache: bool = False, enhance_hf: bool = False, step_hook=None):
+        """Video continuation: the last num_cond_frames frames of `video` become the first num_cond_latents = 1 + (num_cond_frames - 1)
+        // 4 latent frames, kept clean (timestep 0) while the remaining frames are denoised; the result is a num_frames video that
+        starts with them.  use_kv_cache (the default, PIPE:1195-1199): the condition frames go through the DiT ONCE
+        (dit.cache_condition), every step then runs the noise frames only on that resident cache (dit.forward_cached), and the
+        condition latents are put back in front at the end (PIPE:1254-1255).  use_kv_cache=False: every step runs all frames through
+        the plain call (PIPE:1215-1216) and steps the noise frames (PIPE:1248).  CFG-zero and the distilled schedule as in
+        generate_i2v.  The latents are held in the DiT dtype as the reference's are (PIPE:1181), so the uncached loop rounds them to
+        it after every step (PIPE:1248 writes into them) while the cached loop carries the scheduler's fp32 result (PIPE:1246).
+        Not built: offload_kv_cache (the cache stays on the GPU), enhance_hf (the 10-step uniform tail of PIPE:1157-1166; the
+        reference's default), several videos per prompt."""
+        if offload_kv_cache:
+            raise NotImplementedError("offload_kv_cache: the condition cache stays on the GPU")
+        if enhance_hf:
+            raise NotImplementedError("enhance_hf (PIPE:1157-1166) is not built")
+        dev, sch = self.device, self.scheduler
+        ssp = self.vae_scale_factor_spatial * 2
+        if height % ssp != 0 or width % ssp != 0:
+            raise ValueError(f"`height and width` have to be divisible by {ssp} but are {height} and {width}.")  # PIPE:199-201
+        if num_frames % self.vae_scale_factor_temporal != 1:
+            num_frames = num_frames // self.vae_scale_factor_temporal * self.vae_scale_factor_temporal + 1  # PIPE:1092-1096
+        num_frames = max(num_frames, 1)
+        ncl = 1 + (num_cond_frames - 1) // self.vae_scale_factor_temporal  # PIPE:1189
+        if num_cond_frames < 1 or ncl >= (num_frames - 1) // self.vae_scale_factor_temporal + 1:
+            raise ValueError(f"num_cond_frames = {num_cond_frames} must be >= 1 and leave at least one of the {num_frames} frames to generate")
+        self._guidance_scale = guidance_scale
+        do_cfg = self.do_classifier_free_guidance
+        dit_dtype = self.dit.dtype
+        pe = prompt_embeds.to(dev, dit_dtype)
+        pm = prompt_attention_mask.to(dev)
+        if do_cfg:
+            if negative_prompt_embeds is None:
+                raise ValueError("classifier-free guidance (guidance_scale > 1) needs the negative prompt embeddings")
+            pe = torch.cat([negative_prompt_embeds.to(dev, dit_dtype), pe], dim=0)  # PIPE:1148-1150
+            pm = torch.cat([negative_prompt_attention_mask.to(dev), pm], dim=0)
+        # PIPE:1152-1155
+        sch.set_timesteps(num_inference_steps, sigmas=self.get_timesteps_sigmas(num_inference_steps, use_distill=use_distill), device=dev)
+        timesteps = sch.timesteps
+        # PIPE:1168-1185
+        vid = self._preprocess_video(video, height, width).to(dev, dit_dtype)
+        latents = self.prepare_latents_video(vid, 1, self.dit.config.in_channels, height, width, num_frames, num_cond_frames, dit_dtype,
+                                             generator, latents)
+        cache = None
+        if use_kv_cache:  # PIPE:1195-1199
+            cond_latents = latents[:, :, :ncl]
+            cache = self.dit.cache_condition(cond_latents[0])  # one video per call: the CFG pair shares it (LCA:163-165)
+            latents = latents[:, :, ncl:]
+        for i, t in enumerate(timesteps):  # PIPE:1204-1252
+            if step_hook is not None:
+                step_hook(i, "start")
+            sch.derivative_history = []
+            x_in = ops.cast(latents, dit_dtype)
+            if do_cfg:
+                x_in = torch.cat([x_in] * 2)
+            ts = t.expand(x_in.shape[0]).to(dit_dtype).unsqueeze(-1).repeat(1, x_in.shape[2])
+            if use_kv_cache:
+                noise_pred = self.dit.forward_cached(x_in, ts, pe, pm, cache)
+            else:
+                ts[:, :ncl] = 0
+                noise_pred = self.dit(hidden_states=x_in, timestep=ts, encoder_hidden_states=pe, encoder_attention_mask=pm,
+                                      num_cond_latents=ncl)
+            if do_cfg:  # CFG-zero (PIPE:1227-1239) and the sign flip of PIPE:1242 in one launch per sample
+                u, c = noise_pred.chunk(2)
+                noise_pred = torch.stack([ops.cfg_zero(c[b], u[b], guidance_scale, negate=True) for b in range(c.shape[0])])
+            else:
+                noise_pred = -noise_pred
+            if use_kv_cache:
+                latents = sch.step(noise_pred, t, latents, return_dict=False)[0]  # PIPE:1246
+            else:
+                latents[:, :, ncl:] = sch.step(noise_pred[:, :, ncl:], t, latents[:, :, ncl:], return_dict=False)[0]  # PIPE:1248
+            if step_hook is not None:
+                step_hook(i, "end")
+        if use_kv_cache:
+            latents = torch.cat([cond_latents, latents], dim=2)  # PIPE:1254-1255
+        if output_type == "latent":
+            self._check_vae_range()
+            return latents
+        video_out = self.vae.decode(self._final_latents(latents), return_dict=False)[0]
+        video_out = torch.stack([ops.postprocess_video(v) for v in video_out])  # [B,F,H,W,C] in [0,1]
+        self._check_vae_range()
+        return video_out.cpu().numpy() if output_type == "np" else video_out
+
     # ---- PIPE:1271-1511 ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate_refine(self, stage1_video, height: int, width: int, prompt_embeds: torch.Tensor, prompt_attention_mask: torch.Tensor,
@@ -160,7 +283,8 @@ class LongCatVideoPipeline:
             cond = self.vae.encode(enc_in).latent_dist.sample(generator).to(dev, torch.float32)
             latents[:, :, :ncl] = ops.latent_norm(cond, mean, std)
         elif num_cond_frames > 0:
-            raise ValueError("num_cond_frames > 0 needs the conditioning image (video conditioning is not built)")
+            raise ValueError("num_cond_frames > 0 needs the conditioning image (the refine pass takes no conditioning video; "
+                             "generate_vc continues one)")
         # PIPE:1464-1497
         for i, t in enumerate(timesteps):
             if step_hook is not None:
