@@ -333,6 +333,13 @@ int wf_refine_upsample_u8(const void* frames_u8, float* out, int F, int H0, int 
 /* ---- LongCat block-sparse attention of the 720p refine pass (longcat_video/block_sparse_attention/bsa_interface.py = BSA) --------- */
 /* mean_pooling_compression (BSA:169-179): in bf16 [H][L][128] -> out bf16 [H][L/block][128], mean of each block of 64 / 128 tokens. */
 int wf_lc_mean_pool_blocks(const void* in, void* out, int H, int L, int block, void* stream);
+/* The same pooling (BSA:169-179) appended into a region of a wider destination: head h's L rows start at in + h * in_head_stride_rows
+ * rows, their L / block means become blocks [b0, b0 + L / block) of out bf16 [H][out_head_stride_blocks][128]; no other block of out
+ * is read or written.  Arithmetic and rounding of wf_lc_mean_pool_blocks (the same bits with b0 = 0 and dense strides).  WF_EINVAL
+ * before any device work for: non-positive sizes, block not 64 / 128, L % block, in_head_stride_rows < L, b0 < 0 or b0 + L / block >
+ * out_head_stride_blocks, null or not 16-byte aligned pointers. */
+int wf_lc_mean_pool_blocks_at(const void* in, int64_t in_head_stride_rows, void* out, int out_head_stride_blocks, int b0, int H, int L,
+                              int block, void* stream);
 /* Block selection (BSA:211-224, `torch.topk(score, int((1 - sparsity) * n_k))`) fused with the list building of the sparse kernel:
  * scores bf16 [heads][n_q][ld] (n_k valid columns: the gating products of BSA:181-185) -> for every group of g = 256 / block consecutive
  * query blocks the ascending union of their n_sel best key blocks, entry = physical_block * 2^g + sum_i 2^i [selected by the i-th query

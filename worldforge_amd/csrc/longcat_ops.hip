@@ -171,13 +171,13 @@ __global__ void k_lc_swiglu(const uint16_t* __restrict__ in, long ld, uint16_t* 
   }
 }
 
-// in bf16 [H][L][128] -> out bf16 [H][L / 128][128]: mean over each block of 128 consecutive rows, fp32 accumulation, one rounding
-// (torch's mean on a bf16 tensor; bsa_interface.py:169-179).  grid (L / 128, H), 256 threads = 16 row groups x 16 column chunks.
-__global__ __launch_bounds__(256) void k_lc_mean_pool(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, int L, int block) {
-  __shared__ float sm[16][128];
-  const int blk = blockIdx.x, head = blockIdx.y;
+// Mean pooling of key / query blocks (torch's mean on a bf16 tensor; bsa_interface.py:169-179): fp32 accumulation, one rounding.  Both
+// kernels below run ONE body, so their sums, their order and their rounding cannot drift apart: 256 threads = 16 row groups x 16
+// column chunks; pool_partial_sums leaves the 16 groups' partial sums of the `block` rows at `base` in sm, pool_mean adds them in
+// group order for one column and rounds.
+__device__ __forceinline__ void pool_partial_sums(const uint16_t* __restrict__ base, int block, float (*sm)[128]) {
   const int ch = threadIdx.x & 15, grp = threadIdx.x >> 4;
-  const uint16_t* base = in + ((size_t)head * L + (size_t)blk * block) * 128 + ch * 8;
+  base += ch * 8;
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int i = 0; i < block / 16; ++i) {
     float v[8];
@@ -188,11 +188,36 @@ __global__ __launch_bounds__(256) void k_lc_mean_pool(const uint16_t* __restrict
 #pragma unroll
   for (int k = 0; k < 8; ++k) sm[grp][ch * 8 + k] = acc[k];
   __syncthreads();
-  if (threadIdx.x < 128) {
-    float t = 0.f;
+}
+__device__ __forceinline__ uint16_t pool_mean(const float (*sm)[128], int col, int block) {
+  float t = 0.f;
 #pragma unroll
-    for (int g = 0; g < 16; ++g) t += sm[g][threadIdx.x];
-    out[((size_t)head * (L / block) + blk) * 128 + threadIdx.x] = f32_to_bf16(t / (float)block);
+  for (int g = 0; g < 16; ++g) t += sm[g][col];
+  return f32_to_bf16(t / (float)block);
+}
+
+// in bf16 [H][L][128] -> out bf16 [H][L / block][128].  grid (L / block, H).
+__global__ __launch_bounds__(256) void k_lc_mean_pool(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, int L, int block) {
+  __shared__ float sm[16][128];
+  const int blk = blockIdx.x, head = blockIdx.y;
+  pool_partial_sums(in + ((size_t)head * L + (size_t)blk * block) * 128, block, sm);
+  if (threadIdx.x < 128) out[((size_t)head * (L / block) + blk) * 128 + threadIdx.x] = pool_mean(sm, threadIdx.x, block);
+}
+
+// The same pooling into a REGION of a wider destination (the block-ordered condition cache of the refine pass: the pooled means of
+// a step's key blocks are appended behind the resident ones).  Head h's rows start at in + h * in_stride rows; block blk's mean lands
+// at out[h][b0 + blk]; the 128 means leave as 16 16-byte stores (thread c < 16 owns columns 8c .. 8c + 7).
+__global__ __launch_bounds__(256) void k_lc_mean_pool_at(const uint16_t* __restrict__ in, long in_stride, uint16_t* __restrict__ out,
+                                                         int out_stride, int b0, int block) {
+  __shared__ float sm[16][128];
+  const int blk = blockIdx.x, head = blockIdx.y;
+  pool_partial_sums(in + ((size_t)head * in_stride + (size_t)blk * block) * 128, block, sm);
+  if (threadIdx.x < 16) {
+    uint32_t o[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = pool_mean(sm, threadIdx.x * 8 + k, block);
+    reinterpret_cast<u32x4*>(out + ((size_t)head * out_stride + b0 + blk) * 128)[threadIdx.x] =
+        u32x4{o[0] | (o[1] << 16), o[2] | (o[3] << 16), o[4] | (o[5] << 16), o[6] | (o[7] << 16)};
   }
 }
 
@@ -450,6 +475,22 @@ extern "C" int wf_lc_mean_pool_blocks(const void* in, void* out, int H, int L, i
   WF_CHECK_ARG(H > 0 && L > 0 && L % block == 0, "wf_lc_mean_pool_blocks: L (%d) must be whole %d-token blocks", L, block);
   hipLaunchKernelGGL(k_lc_mean_pool, dim3(L / block, H), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)in, (uint16_t*)out, L, block);
   WF_LAUNCH_CHECK("wf_lc_mean_pool_blocks");
+  return WF_OK;
+}
+
+extern "C" int wf_lc_mean_pool_blocks_at(const void* in, int64_t in_head_stride_rows, void* out, int out_head_stride_blocks, int b0,
+                                         int H, int L, int block, void* stream) {
+  WF_CHECK_ARG(in && out, "wf_lc_mean_pool_blocks_at: null pointer");
+  WF_CHECK_ARG(block == 128 || block == 64, "wf_lc_mean_pool_blocks_at: block must be 128 or 64");
+  WF_CHECK_ARG(H > 0 && L > 0 && L % block == 0, "wf_lc_mean_pool_blocks_at: L (%d) must be whole %d-token blocks", L, block);
+  WF_CHECK_ARG(in_head_stride_rows >= L, "wf_lc_mean_pool_blocks_at: in_head_stride_rows must be >= L=%d", L);
+  WF_CHECK_ARG(b0 >= 0 && out_head_stride_blocks > 0 && (int64_t)b0 + L / block <= out_head_stride_blocks,
+               "wf_lc_mean_pool_blocks_at: blocks [%d, %d + %d) must lie inside the %d blocks of a head", b0, b0, L / block,
+               out_head_stride_blocks);
+  WF_CHECK_ARG((((uintptr_t)in | (uintptr_t)out) & 15) == 0, "wf_lc_mean_pool_blocks_at: 16-byte alignment");
+  hipLaunchKernelGGL(k_lc_mean_pool_at, dim3(L / block, H), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)in,
+                     (long)in_head_stride_rows, (uint16_t*)out, out_head_stride_blocks, b0, block);
+  WF_LAUNCH_CHECK("wf_lc_mean_pool_blocks_at");
   return WF_OK;
 }
 

@@ -23,7 +23,9 @@ cross-attention: it depends on neither the noise tokens, the prompt nor the step
 in the attention kernel's layout (LongCatCondCache); `forward_tokens_cached` / `forward_cached` then run the noise frames only, appending
 their keys behind the cached ones (wf_lc_norm_heads at a row offset, wf_v_transpose_at) in front of the one noise-query attention launch
 of the uncached forward.  A cache is bound to the weights it was built with (weights version, adapters, linear_precision) and to its
-latent size.  Not built: continuation under sequence parallelism or block-sparse attention, CPU offload of the cache.
+latent size.  `cache_condition_blocks` / `forward_tokens_cached_blocks` / `forward_cached_blocks` are the same for a model with
+block-sparse attention on (the refine pass of a continued video): a LongCatBlockCondCache holds K / V^T and the pooled key-block means
+in 3D-block token order.  Not built: continuation under sequence parallelism, CPU offload of the cache.
 """
 from __future__ import annotations
 
@@ -144,6 +146,28 @@ class LongCatCondCache:
     nc: int                # condition tokens = ncl * tokens per frame
     latent_hw: Tuple[int, int]
     owner: object          # the model's token, and what its weights were when the cache was built:
+    wver: int
+    loras: Tuple[str, ...]
+    linear_precision: str
+
+
+@dataclass(eq=False)
+class LongCatBlockCondCache:
+    """The condition cache of the block-sparse refine pass (cache_condition_blocks): every tensor in 3D-BLOCK token order, in which
+    the condition tokens are the first nc rows of every (condition + noise) grid (bsa_interface.py:600-604 orders by frame chunk first
+    and ncl is whole chunks), so nc is whole blocks and whole 64-key tiles.  Besides K / V^T it keeps the pooled key-block means
+    (bsa_interface.py:169-179): the gating of every later step scores its query blocks against them."""
+    k: torch.Tensor        # bf16 [depth, H, nc, 128], normalised and rotated
+    vt: torch.Tensor       # bf16 [depth, H, nc / 64, 128, 64]
+    kcmp: torch.Tensor     # bf16 [depth, H, nc / block, 128]: mean of every key block
+    bsa_indices: list      # per DiT block the condition-query selection of the build (what last_bsa_indices held; read by tests)
+    ncl: int
+    nc: int
+    latent_hw: Tuple[int, int]
+    chunk: Tuple[int, int, int]
+    sparsity: Optional[float]
+    cdf_threshold: Optional[float]
+    owner: object
     wver: int
     loras: Tuple[str, ...]
     linear_precision: str
@@ -542,11 +566,13 @@ class LongCatVideoTransformer3DModel:
         LCA:123-138 is by GLOBAL token index: a rank's rows below the first frame boundary are condition queries (keys < nc), the rest
         noise queries.
 
-        vc (video continuation, single GPU, dense attention) = ("build", cache): x_in holds condition frames only -- the stream of
+        vc (video continuation, single GPU) = ("build", cache): x_in holds condition frames only -- the stream of
         LCA:127-131 / PIPE:336-348 (no caption, no cross-attention, no final layer), whose K / V^T / norm bound of every block are
         written straight into `cache`; nothing lands in result.  ("use", cache): x_in holds the noise frames only; the cache's keys are
         copied to the front of a working K / V^T pair, this step's keys are appended behind them, and everything else runs on the
-        noise rows."""
+        noise rows.  With block-sparse attention on (a LongCatBlockCondCache) both modes run in block order: the build also keeps
+        the pooled key-block means and its selection, a step appends its own means behind the cached ones (wf_lc_mean_pool_blocks_at)
+        and scores / selects / attends for the noise query blocks only, over all (nc + L) / block key blocks."""
         cfg, W, dev = self.cfg, self._wl, self.device
         bf, f32 = torch.bfloat16, torch.float32
         Cin, T, Hh, Ww = x_in.shape
@@ -565,7 +591,7 @@ class LongCatVideoTransformer3DModel:
         cos, sin = self._rope_tables(fc + T, h2, w2)
         _buf = lambda name, shape, dtype, zero=False: self._buf(name + tag, shape, dtype, zero)  # noqa: E731
         comm = self.comm
-        use_bsa = self._bsa and T > 1  # LCA:57: "bsa will not be used in image training / sampling"
+        use_bsa = self._bsa and fc + T > 1  # LCA:57: "bsa will not be used in image training / sampling"
         gidx = perm = pos = None
         blk = 64
         if use_bsa:
@@ -581,13 +607,25 @@ class LongCatVideoTransformer3DModel:
             if ncl % cq[0] or (T - ncl) % cq[0]:
                 raise ValueError(f"block-sparse attention needs the condition ({ncl}) and noise ({T - ncl}) latent frames to be "
                                  f"multiples of {cq[0]} (the reference pads them: pipeline_longcat_video.py:1417-1419)")
-            perm, pos = bsa.block_permutation(T, h2, w2, cq, dev)
             blk = cq[0] * cq[1] * cq[2]
-            key = ("blk", T, h2, w2, tuple(cq))
-            if key not in self._rope:
-                pl = perm.long()
-                self._rope[key] = (cos[pl].contiguous(), sin[pl].contiguous(), (perm // tpf).to(torch.int32).contiguous())
-            cos, sin, gidx = self._rope[key]
+            if kc:
+                # a cached step: its rows are rows kc.. of the (fc + T) grid's block order -- that grid's permuted RoPE tables (`cos` /
+                # `sin` are that grid's; sliced at kc below), and its permutation / frame indices / inverse permutation restricted to
+                # those rows, counted from the first noise token / frame
+                key = ("blk_vc", fc, T, h2, w2, tuple(cq))
+                if key not in self._rope:
+                    pf, qf = bsa.block_permutation(fc + T, h2, w2, cq, dev)
+                    pl = pf.long()
+                    self._rope[key] = (cos[pl].contiguous(), sin[pl].contiguous(), (pf[kc:] // tpf - fc).to(torch.int32).contiguous(),
+                                       (pf[kc:] - kc).contiguous(), (qf[kc:] - kc).contiguous())
+                cos, sin, gidx, perm, pos = self._rope[key]
+            else:
+                perm, pos = bsa.block_permutation(T, h2, w2, cq, dev)
+                key = ("blk", T, h2, w2, tuple(cq))
+                if key not in self._rope:
+                    pl = perm.long()
+                    self._rope[key] = (cos[pl].contiguous(), sin[pl].contiguous(), (perm // tpf).to(torch.int32).contiguous())
+                cos, sin, gidx = self._rope[key]
         if comm is not None:
             from .parallel import ShardPlan, gather_rows, shard_plan
             if use_bsa:  # whole 256-row query groups (two 128-token / four 64-token blocks) per rank
@@ -667,6 +705,7 @@ class LongCatVideoTransformer3DModel:
                 kh = _buf("kh_vc", (H, Sp, 128), bf, zero=True)
                 vt = _buf("vt_vc", (H, Sp // 64, 128, 64), bf, zero=True)
                 km = _buf("kmax2_vc", (H,), f32) if use_bounds else None
+                kcw = _buf("kcmp_vc", (H, Sp // blk, 128), bf) if use_bsa else None
         else:
             kh = _buf("kh", (H, Sp, 128), bf, zero=True)
             vt = _buf("vt", (H, Sp // 64, 128, 64), bf)
@@ -727,9 +766,24 @@ class LongCatVideoTransformer3DModel:
                 # bf16 block scores -> top-k / cdf selection per query block -> sparse attention over the selected key blocks
                 self._heads(qkv, 0, W[p + "attn.q_norm"], cos, sin, qh_c, 0, nc)
                 self._heads(qkv, 0, W[p + "attn.q_norm"], cos, sin, qh_n, nc, L)
-                self._heads(qkv, C, W[p + "attn.k_norm"], cos, sin, kh, 0, L)
-                self._vt(qkv, 2 * C, vt, L)
-                kcmp = bsa.mean_pool(kh, blk)  # this rank's key blocks (zero rows past the last token pool to zero blocks)
+                if vc is not None and not build:
+                    # the cached keys, values and pooled means in front (kc is whole blocks), this step's appended behind them
+                    kh[:, :kc].copy_(cache.k[i])
+                    vt[:, :kc // 64].copy_(cache.vt[i])
+                    kcw[:, :kc // blk].copy_(cache.kcmp[i])
+                    self._heads(qkv, C, W[p + "attn.k_norm"], cos, sin, kh[:, kc:], 0, L, lout=Sp)
+                    self._vt_at(qkv, 2 * C, vt, kc, L)
+                    call("wf_lc_mean_pool_blocks_at", kh[:, kc:].data_ptr(), Sp, kcw.data_ptr(), Sp // blk, kc // blk, H, L, blk,
+                         ops.stream())
+                    kcmp = kcw
+                else:
+                    if build:
+                        kh, vt = cache.k[i], cache.vt[i]
+                    self._heads(qkv, C, W[p + "attn.k_norm"], cos, sin, kh, 0, L)
+                    self._vt(qkv, 2 * C, vt, L)
+                    kcmp = bsa.mean_pool(kh, blk)  # this rank's key blocks (zero rows past the last token pool to zero blocks)
+                    if build:
+                        cache.kcmp[i].copy_(kcmp)
                 kk, vv = kh, vt
                 if comm is not None:
                     evs = (comm.all_gather_async(kh_all, kh), comm.all_gather_async(vt_all, vt))
@@ -756,6 +810,10 @@ class LongCatVideoTransformer3DModel:
                         bsa.sparse_attention(qrows, kk, vv, orows, idx, scale, nkb, lens, blk)
                         picked.append(idx if lens is None else (idx, lens))
                 self.last_bsa_indices.append(picked)
+                if build:
+                    cache.bsa_indices.append(picked[0])
+                    if i == cfg.depth - 1:
+                        return  # (the dense build returns in front of its last attention; this one keeps the last selection too)
             else:
                 self._heads(qkv, 0, W[p + "attn.q_norm"], cos, sin, qh_c, 0, nc, out_scale=q_scale)
                 self._heads(qkv, 0, W[p + "attn.q_norm"], cos, sin, qh_n, nc, L, out_scale=q_scale)
@@ -847,7 +905,7 @@ class LongCatVideoTransformer3DModel:
             yo = gather_rows(comm, yo, plan).contiguous()
         if use_bsa:  # velocity rows back to (T, H, W) order: bsa_interface.py:606-610 (fp32 rows moved as 16-byte chunks)
             yt = torch.empty_like(yo)
-            call("wf_gather_rows_bf16", yo.data_ptr(), 2 * yo.stride(0), pos.data_ptr(), yt.data_ptr(), 2 * yt.stride(0), L_all,
+            call("wf_gather_rows_bf16", yo.data_ptr(), 2 * yo.stride(0), pos.data_ptr(), yt.data_ptr(), 2 * yt.stride(0), L_all - kc,
                  2 * yo.shape[1], ops.stream())
             yo = yt
         out = torch.empty((cfg.out_channels, T, Hh, Ww), dtype=f32, device=dev)
@@ -879,8 +937,8 @@ class LongCatVideoTransformer3DModel:
         if self.comm is not None:
             raise NotImplementedError("video continuation under sequence parallelism (`comm`) is not built")
         if self._bsa:
-            raise NotImplementedError("video continuation with block-sparse attention is not built (the reference's refine pass does "
-                                      "not use the KV cache: disable_bsa() first)")
+            raise NotImplementedError("the dense condition cache does not serve block-sparse attention: disable_bsa() first, or use "
+                                      "cache_condition_blocks() / forward_cached_blocks()")
 
     def cache_condition(self, cond_latents: torch.Tensor) -> LongCatCondCache:
         """PIPE:336-348 (`_cache_clean_latents`: timestep 0, skip_crs_attn, return_kv).  cond_latents [16, ncl, Hh, Ww] (normalised
@@ -906,6 +964,8 @@ class LongCatVideoTransformer3DModel:
 
     def _check_cache(self, cache: LongCatCondCache, latent_hw):
         self._vc_guard()
+        if not isinstance(cache, LongCatCondCache):
+            raise ValueError("forward_cached / forward_tokens_cached take the dense LongCatCondCache of cache_condition()")
         if cache.owner is not self._token or cache.wver != self._wver or cache.loras != tuple(self.active_loras) \
                 or cache.linear_precision != self.linear_precision:
             raise ValueError("the condition cache was built with other weights (another model, a weight load / weights_changed(), a LoRA "
@@ -932,6 +992,88 @@ class LongCatVideoTransformer3DModel:
         conversions of __call__; the samples run one after the other on the one cache.  -> fp32 [B, 16, T, Hh, Ww]."""
         samples = self._batch_samples(hidden_states, timestep, encoder_hidden_states, encoder_attention_mask)
         return torch.stack([self.forward_tokens_cached(*smp, cache) for smp in samples])
+
+    # ---- the same on a block-ordered cache, for the block-sparse refine pass (PIPE:1271-1511 with a conditioning video) -----------
+    def _vc_blocks_guard(self):
+        if self.comm is not None:
+            raise NotImplementedError("the block-ordered condition cache under sequence parallelism (`comm`) is not built")
+        if not self._bsa:
+            raise NotImplementedError("the block-ordered condition cache belongs to block-sparse attention (enable_bsa()); a dense "
+                                      "model caches with cache_condition() / forward_cached()")
+        cq, ck = self.bsa_params["chunk_3d_shape_q"], self.bsa_params["chunk_3d_shape_k"]
+        if list(cq) != list(ck):
+            raise NotImplementedError("different query / key block shapes")
+        return tuple(int(c) for c in cq)
+
+    def _vc_blocks_selection(self, n_key_blocks: int):
+        """(sparsity, cdf_threshold) of bsa_params; the cdf rule is only built on its fused kernel."""
+        from . import bsa
+        sp, cdf = self.bsa_params.get("sparsity"), self.bsa_params.get("cdf_threshold")
+        if cdf is not None and n_key_blocks > bsa.TOPK_MAX_BLOCKS:
+            raise NotImplementedError(f"cdf_threshold over more than {bsa.TOPK_MAX_BLOCKS} key blocks on a condition cache is not built")
+        return (None if sp is None else float(sp)), (None if cdf is None else float(cdf))
+
+    def cache_condition_blocks(self, cond_latents: torch.Tensor) -> LongCatBlockCondCache:
+        """cache_condition for a model with block-sparse attention on: cond_latents [16, ncl, Hh, Ww], ncl a whole number (> 1 frame)
+        of chunk[0]-frame blocks.  The condition stream stays independent under block-sparse attention -- its queries see condition
+        keys only (LCA:124-131), select among condition key blocks only, skip cross-attention and carry timestep 0 -- so it is run
+        once, in block order, and K / V^T / the pooled block means of every DiT block stay resident."""
+        cq = self._vc_blocks_guard()
+        cfg, dev = self.cfg, self.device
+        x = cond_latents if cond_latents.dtype == torch.bfloat16 else ops.cast(cond_latents.contiguous(), torch.bfloat16)
+        x = x.to(dev).contiguous()
+        _, ncl, Hh, Ww = x.shape
+        if ncl < 2 or ncl % cq[0]:
+            raise ValueError(f"the block-ordered condition cache needs at least 2 condition latent frames in whole {cq[0]}-frame blocks, "
+                             f"not {ncl} (the reference pads them: pipeline_longcat_video.py:1417-1419)")
+        blk = cq[0] * cq[1] * cq[2]
+        nc = ncl * (Hh // 2) * (Ww // 2)
+        sp, cdf = self._vc_blocks_selection(nc // blk)
+        H, bf = cfg.num_heads, torch.bfloat16
+        cache = LongCatBlockCondCache(
+            k=torch.empty((cfg.depth, H, nc, 128), dtype=bf, device=dev),
+            vt=torch.empty((cfg.depth, H, nc // 64, 128, 64), dtype=bf, device=dev),
+            kcmp=torch.empty((cfg.depth, H, nc // blk, 128), dtype=bf, device=dev), bsa_indices=[],
+            ncl=ncl, nc=nc, latent_hw=(Hh, Ww), chunk=cq, sparsity=sp, cdf_threshold=cdf, owner=self._token, wver=self._wver,
+            loras=tuple(self.active_loras), linear_precision=self.linear_precision)
+        for _ in self._forward_steps(x, [0.0] * ncl, None, None, ncl, "", [None], "gather", vc=("build", cache)):
+            pass
+        return cache
+
+    def _check_block_cache(self, cache: LongCatBlockCondCache, latent_hw, T: int):
+        cq = self._vc_blocks_guard()
+        if not isinstance(cache, LongCatBlockCondCache):
+            raise ValueError("forward_cached_blocks / forward_tokens_cached_blocks take the LongCatBlockCondCache of cache_condition_blocks()")
+        if cache.owner is not self._token or cache.wver != self._wver or cache.loras != tuple(self.active_loras) \
+                or cache.linear_precision != self.linear_precision:
+            raise ValueError("the condition cache was built with other weights (another model, a weight load / weights_changed(), a LoRA "
+                             "switch or another linear_precision since): build it again with cache_condition_blocks()")
+        if tuple(latent_hw) != tuple(cache.latent_hw):
+            raise ValueError(f"the condition cache holds {cache.latent_hw[0]} x {cache.latent_hw[1]} latent frames, the input is "
+                             f"{latent_hw[0]} x {latent_hw[1]}")
+        blk = cq[0] * cq[1] * cq[2]
+        tpf = (latent_hw[0] // 2) * (latent_hw[1] // 2)
+        if cache.chunk != cq or (cache.sparsity, cache.cdf_threshold) != self._vc_blocks_selection((cache.nc + T * tpf) // blk):
+            raise ValueError("the condition cache was built under other bsa_params (chunk shape, sparsity or cdf_threshold): its block "
+                             "order and its selection are not this model's; build it again with cache_condition_blocks()")
+
+    def forward_tokens_cached_blocks(self, x_in: torch.Tensor, timesteps, caption: torch.Tensor, caption_mask: Optional[torch.Tensor],
+                                     cache: LongCatBlockCondCache) -> torch.Tensor:
+        """forward_tokens_cached under block-sparse attention: x_in [16, T, Hh, Ww] bf16 NOISE frames (T whole chunk[0]-frame blocks)
+        -> velocity [16, T, Hh, Ww] fp32 in (T, H, W) order: the value of the noise frames of forward_tokens(concatenated latents,
+        condition timesteps 0, num_cond_latents = cache.ncl) with block-sparse attention on.  last_bsa_indices[i] then holds one entry,
+        the noise-query selection over all (cache.nc + L) / block key blocks."""
+        self._check_block_cache(cache, x_in.shape[-2:], x_in.shape[1])
+        out = [None]
+        for _ in self._forward_steps(x_in, timesteps, caption, caption_mask, 0, "", out, "gather", vc=("use", cache)):
+            pass
+        return out[0]
+
+    def forward_cached_blocks(self, hidden_states: torch.Tensor, timestep: torch.Tensor, encoder_hidden_states: torch.Tensor,
+                              encoder_attention_mask: Optional[torch.Tensor], cache: LongCatBlockCondCache) -> torch.Tensor:
+        """The batch form: hidden_states [B, 16, T, Hh, Ww] noise frames, the conversions of __call__ -> fp32 [B, 16, T, Hh, Ww]."""
+        samples = self._batch_samples(hidden_states, timestep, encoder_hidden_states, encoder_attention_mask)
+        return torch.stack([self.forward_tokens_cached_blocks(*smp, cache) for smp in samples])
 
     def __call__(self, hidden_states: torch.Tensor, timestep: torch.Tensor, encoder_hidden_states: torch.Tensor,
                  encoder_attention_mask: Optional[torch.Tensor] = None, num_cond_latents: int = 0, return_kv: bool = False,

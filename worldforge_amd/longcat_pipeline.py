@@ -207,19 +207,58 @@ class LongCatVideoPipeline:
         return video_out.cpu().numpy() if output_type == "np" else video_out
 
     # ---- PIPE:1271-1511 ---------------------------------------------------------------------------------------------------
+    @staticmethod
+    def refine_padding(num_cond_frames: int, new_frame_size: int, temporal_scale: int = 4, granularity: int = 4):
+        """PIPE:1414-1424: the refine pass pads the condition and the noise frames to whole blocks of `granularity` latent frames (what
+        block-sparse attention takes).  -> (condition latent frames, frames repeated in front, noise latent frames, frames repeated
+        behind); the condition count is 0 / 0 without condition frames."""
+        import math
+        tsc, gran = temporal_scale, granularity
+        num_noise_frames = new_frame_size - num_cond_frames
+        ncl = added_c = 0
+        if num_cond_frames > 0:
+            ncl = 1 + math.ceil((num_cond_frames - 1) / tsc)
+            ncl = math.ceil(ncl / gran) * gran
+            added_c = 1 + (ncl - 1) * tsc - num_cond_frames
+        nnl = math.ceil(math.ceil(num_noise_frames / tsc) / gran) * gran
+        added_n = nnl * tsc - num_noise_frames
+        return ncl, added_c, nnl, added_n
+
+    @staticmethod
+    def refine_condition_frames(video: torch.Tensor, num_cond_frames: int, added_c: int) -> torch.Tensor:
+        """PIPE:272-276: video [1, 3, F, H, W] -> its last (num_cond_frames - added_c) frames with the first of them repeated added_c
+        times in front: [1, 3, num_cond_frames, H, W], num_cond_frames being the PADDED count."""
+        take = num_cond_frames - added_c
+        if take < 1 or video.shape[2] < take:
+            raise ValueError(f"the conditioning video has {video.shape[2]} frames, num_cond_frames asks for its last {take}")
+        enc_in = video[0][:, -take:].unsqueeze(0)
+        enc_in = torch.cat([enc_in[:, :, 0:1].repeat(1, 1, added_c, 1, 1), enc_in], dim=2)
+        assert enc_in.shape[2] == num_cond_frames
+        return enc_in
+
     @torch.no_grad()
     def generate_refine(self, stage1_video, height: int, width: int, prompt_embeds: torch.Tensor, prompt_attention_mask: torch.Tensor,
                         image=None, num_cond_frames: int = 0, num_inference_steps: int = 50, generator=None, output_type: str = "np",
-                        t_thresh: float = 0.5, spatial_refine_only: bool = False, step_hook=None):
+                        t_thresh: float = 0.5, spatial_refine_only: bool = False, step_hook=None, video=None,
+                        use_kv_cache: bool = False):
         """The 720p refine pass: the stage-1 (480p) video is up-sampled, encoded, mixed with noise at t_thresh and denoised from there
         without CFG, the DiT running with block-sparse self-attention and the refinement LoRA, as
         run_longcat_worldforge_single.py:447-451 does: `dit.enable_loras(["refinement_lora"])` and `dit.enable_bsa()` on the resident
         model that ran stage 1 (longcat_dit.load_lora / enable_loras; or a model built with the adapter folded in by fold_lora).  stage1_video: uint8 frames [F, H0, W0, 3] (tensor / array / list of arrays);
-        image: the conditioning first frame at the target size or None.  Returns frames [1, F', H, W, 3] in [0, 1]."""
-        import math
-
+        image: the conditioning first frame at the target size or None.  video: the already refined frames of the previous window
+        (uint8 [F, H, W, 3] or float [3, F, H, W] at the target size): its last num_cond_frames frames condition this one (PIPE:272),
+        front-padded to whole 4-latent-frame blocks by repeating their first frame (PIPE:1417-1419, 274-275).  use_kv_cache (off by
+        default: the reference does not cache here): the condition latents go through the block-sparse DiT once
+        (dit.cache_condition_blocks), every step runs the noise frames only (dit.forward_cached_blocks), and the condition latents
+        are put back in front before decoding.  Returns frames [1, F', H, W, 3] in [0, 1]."""
         from ._ffi import call
         dev, sch = self.device, self.scheduler
+        if image is not None and video is not None:  # PIPE:1332
+            raise ValueError("Cannot provide both `image and video` at the same time. Please provide only one.")
+        if video is not None and num_cond_frames <= 0:
+            raise ValueError("a conditioning video needs num_cond_frames > 0 (how many of its last frames condition the window)")
+        if use_kv_cache and num_cond_frames <= 0:
+            raise ValueError("use_kv_cache caches the condition frames' stream: it needs num_cond_frames > 0 and an image or a video")
         ssp = self.vae_scale_factor_spatial * 2 * 4  # PIPE:1336
         if height % ssp != 0 or width % ssp != 0:
             raise ValueError(f"`height and width` have to be divisible by {ssp} but are {height} and {width}.")
@@ -245,16 +284,8 @@ class LongCatVideoPipeline:
         up = torch.empty((1, 3, new_frame_size, height, width), dtype=torch.float32, device=dev)
         call("wf_refine_upsample_u8", frames.data_ptr(), up.data_ptr(), nf, H0, W0, new_frame_size, height, width, ops.stream())
         # PIPE:1415-1435: pad to the block-sparse granularity (4 latent frames), encode, mix with noise
-        gran, tsc = 4, self.vae_scale_factor_temporal
-        num_noise_frames = new_frame_size - num_cond_frames
-        ncl = added_c = 0
-        if num_cond_frames > 0:
-            ncl = 1 + math.ceil((num_cond_frames - 1) / tsc)
-            ncl = math.ceil(ncl / gran) * gran
-            added_c = 1 + (ncl - 1) * tsc - num_cond_frames
-            num_cond_frames = num_cond_frames + added_c
-        nnl = math.ceil(math.ceil(num_noise_frames / tsc) / gran) * gran
-        added_n = nnl * tsc - num_noise_frames
+        ncl, added_c, nnl, added_n = self.refine_padding(num_cond_frames, new_frame_size, self.vae_scale_factor_temporal)
+        num_cond_frames = num_cond_frames + added_c
         up = torch.cat([up[:, :, 0:1].repeat(1, 1, added_c, 1, 1), up, up[:, :, -1:].repeat(1, 1, added_n, 1, 1)], dim=2)
         mean, std = self.vae.config.latents_mean, self.vae.config.latents_std
         samp = self.vae.encode(up if getattr(self.vae, "dtype", torch.float32) == torch.float32 else ops.cast(up, self.vae.dtype)) \
@@ -282,25 +313,40 @@ class LongCatVideoPipeline:
             assert enc_in.shape[2] == num_cond_frames
             cond = self.vae.encode(enc_in).latent_dist.sample(generator).to(dev, torch.float32)
             latents[:, :, :ncl] = ops.latent_norm(cond, mean, std)
+        elif video is not None:  # PIPE:272-284: the last frames of the video, front-padded likewise
+            vid = self._preprocess_video(video, height, width).to(dev, dit_dtype)
+            enc_in = self.refine_condition_frames(vid, num_cond_frames, added_c)
+            cond = self.vae.encode(enc_in).latent_dist.sample(generator).to(dev, torch.float32)
+            latents[:, :, :ncl] = ops.latent_norm(cond, mean, std)
         elif num_cond_frames > 0:
-            raise ValueError("num_cond_frames > 0 needs the conditioning image (the refine pass takes no conditioning video; "
-                             "generate_vc continues one)")
+            raise ValueError("num_cond_frames > 0 needs the conditioning image or the conditioning video")
+        cache = cond_latents = None
+        if use_kv_cache:
+            cond_latents = latents[:, :, :ncl]
+            cache = self.dit.cache_condition_blocks(cond_latents[0])
+            latents = latents[:, :, ncl:].contiguous()
         # PIPE:1464-1497
         for i, t in enumerate(timesteps):
             if step_hook is not None:
                 step_hook(i, "start")
             ts = t.expand(latents.shape[0]).to(dit_dtype).unsqueeze(-1).repeat(1, latents.shape[2])
-            ts[:, :ncl] = 0
-            noise_pred = -self.dit(hidden_states=ops.cast(latents, dit_dtype), timestep=ts, encoder_hidden_states=pe,
-                                   encoder_attention_mask=pm, num_cond_latents=ncl)
-            latents[:, :, ncl:] = sch.step(noise_pred[:, :, ncl:], t, latents[:, :, ncl:], return_dict=False)[0]
+            if cache is not None:
+                noise_pred = -self.dit.forward_cached_blocks(ops.cast(latents, dit_dtype), ts, pe, pm, cache)
+                latents = sch.step(noise_pred, t, latents, return_dict=False)[0]
+            else:
+                ts[:, :ncl] = 0
+                noise_pred = -self.dit(hidden_states=ops.cast(latents, dit_dtype), timestep=ts, encoder_hidden_states=pe,
+                                       encoder_attention_mask=pm, num_cond_latents=ncl)
+                latents[:, :, ncl:] = sch.step(noise_pred[:, :, ncl:], t, latents[:, :, ncl:], return_dict=False)[0]
             if step_hook is not None:
                 step_hook(i, "end")
+        if cache is not None:
+            latents = torch.cat([cond_latents, latents.to(cond_latents.dtype)], dim=2)
         if output_type == "latent":
             self._check_vae_range()
             return latents
-        video = self.vae.decode(self._final_latents(latents), return_dict=False)[0]
-        video = torch.stack([ops.postprocess_video(v) for v in video])[:, added_c: new_frame_size + added_c]  # PIPE:1505
+        out = self.vae.decode(self._final_latents(latents), return_dict=False)[0]
+        video = torch.stack([ops.postprocess_video(v) for v in out])[:, added_c: new_frame_size + added_c]  # PIPE:1507
         self._check_vae_range()
         return video.cpu().numpy() if output_type == "np" else video
 
