@@ -356,6 +356,51 @@ def diffusers_key_map(num_layers: int) -> Dict[str, str]:
     return m
 
 
+def config_from_diffusers(c: dict) -> DiTConfig:
+    """The fields of a diffusers `transformer/config.json` (see WanTransformer3DModel.from_pretrained) -> DiTConfig; missing fields
+    keep the Wan2.1-I2V-14B values."""
+    cfg = DiTConfig.wan_i2v_14b()
+    heads = int(c.get("num_attention_heads", cfg.num_heads))
+    return DiTConfig(dim=heads * int(c.get("attention_head_dim", 128)), ffn_dim=int(c.get("ffn_dim", cfg.ffn_dim)), num_heads=heads,
+                     num_layers=int(c.get("num_layers", cfg.num_layers)), in_dim=int(c.get("in_channels", cfg.in_dim)),
+                     out_dim=int(c.get("out_channels", cfg.out_dim)), freq_dim=int(c.get("freq_dim", cfg.freq_dim)),
+                     text_dim=int(c.get("text_dim", cfg.text_dim)), img_dim=int(c.get("image_dim") or cfg.img_dim),
+                     patch_size=tuple(c.get("patch_size", cfg.patch_size)), eps=float(c.get("eps", cfg.eps)))
+
+
+def expected_diffusers_state_dict(cfg: DiTConfig) -> Dict[str, tuple]:
+    """{diffusers parameter name: shape} of everything load_diffusers_state_dict reads: the modules of diffusers_key_map with the
+    leaves and shapes load_state_dict takes, plus the modulation tables.  Host only (the checkpoint audit)."""
+    d, f, im = cfg.dim, cfg.ffn_dim, cfg.img_dim
+    lin = {"condition_embedder.time_embedder.linear_1": (d, cfg.freq_dim), "condition_embedder.time_embedder.linear_2": (d, d),
+           "condition_embedder.time_proj": (6 * d, d), "condition_embedder.text_embedder.linear_1": (d, cfg.text_dim),
+           "condition_embedder.text_embedder.linear_2": (d, d), "condition_embedder.image_embedder.ff.net.0.proj": (im, im),
+           "condition_embedder.image_embedder.ff.net.2": (d, im), "proj_out": (4 * cfg.out_dim, d)}
+    norm = {"condition_embedder.image_embedder.norm1": im, "condition_embedder.image_embedder.norm2": d}   # LayerNorm: weight + bias
+    rms = {}                                                                                                # RMSNorm: weight only
+    for i in range(cfg.num_layers):
+        b = f"blocks.{i}."
+        for a in ("attn1", "attn2"):
+            for s in ("to_q", "to_k", "to_v", "to_out.0"):
+                lin[f"{b}{a}.{s}"] = (d, d)
+            rms[f"{b}{a}.norm_q"] = rms[f"{b}{a}.norm_k"] = d
+        lin[f"{b}attn2.add_k_proj"] = lin[f"{b}attn2.add_v_proj"] = (d, d)
+        rms[f"{b}attn2.norm_added_k"] = d
+        norm[f"{b}norm2"] = d
+        lin[f"{b}ffn.net.0.proj"], lin[f"{b}ffn.net.2"] = (f, d), (d, f)
+    out = {"patch_embedding.weight": (d, cfg.in_dim) + tuple(cfg.patch_size), "patch_embedding.bias": (d,), "scale_shift_table": (1, 2, d)}
+    for k, (o, i) in lin.items():
+        out[k + ".weight"], out[k + ".bias"] = (o, i), (o,)
+    for k, n in norm.items():
+        out[k + ".weight"] = out[k + ".bias"] = (n,)
+    for k, n in rms.items():
+        out[k + ".weight"] = (n,)
+    for i in range(cfg.num_layers):
+        out[f"blocks.{i}.scale_shift_table"] = (1, 6, d)
+    assert {k.rpartition(".")[0] for k in out if not k.endswith("scale_shift_table")} == set(diffusers_key_map(cfg.num_layers))
+    return out
+
+
 class WanTransformer3DModel:
     dtype = torch.bfloat16
 
@@ -477,13 +522,7 @@ class WanTransformer3DModel:
         cj = os.path.join(folder, "config.json")
         if os.path.exists(cj):
             with open(cj) as f:
-                c = _json.load(f)
-            heads = int(c.get("num_attention_heads", cfg.num_heads))
-            cfg = DiTConfig(dim=heads * int(c.get("attention_head_dim", 128)), ffn_dim=int(c.get("ffn_dim", cfg.ffn_dim)), num_heads=heads,
-                            num_layers=int(c.get("num_layers", cfg.num_layers)), in_dim=int(c.get("in_channels", cfg.in_dim)),
-                            out_dim=int(c.get("out_channels", cfg.out_dim)), freq_dim=int(c.get("freq_dim", cfg.freq_dim)),
-                            text_dim=int(c.get("text_dim", cfg.text_dim)), img_dim=int(c.get("image_dim") or cfg.img_dim),
-                            patch_size=tuple(c.get("patch_size", cfg.patch_size)), eps=float(c.get("eps", cfg.eps)))
+                cfg = config_from_diffusers(_json.load(f))
         return cls(cfg, device, comm=comm, linear_precision=linear_precision).load_diffusers_state_dict(checkpoint.load_dir(folder))
 
     def init_random(self, seed: int = 0):

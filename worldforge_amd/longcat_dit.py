@@ -18,6 +18,10 @@ base copy), so the forward still runs on plain bf16 matrices and a LoRA costs no
 route (a fold before load_state_dict, not undoable).  Block-sparse attention (LCA:57-66; `enable_bsa`, bsa.py)
 and sequence parallelism (`comm`, parallel.py) are built.
 
+Weights: `load_state_dict` (a reference-keyed state dict), `init_random`, or `from_pretrained(folder)` -- `<folder>/dit/config.json` plus
+safetensors files, their headers checked against `expected_state_dict(cfg)` before anything is uploaded, every tensor rounded to bf16
+first as the reference's `torch_dtype=torch.bfloat16` load does (run_longcat_worldforge_single.py:207).
+
 Video continuation (LCA:147-181, PIPE:336-348): `cache_condition` runs the condition frames' stream once (timestep 0, no caption, no
 cross-attention: it depends on neither the noise tokens, the prompt nor the step) and keeps every block's K / V^T / norm bound resident
 in the attention kernel's layout (LongCatCondCache); `forward_tokens_cached` / `forward_cached` then run the noise frames only, appending
@@ -65,6 +69,63 @@ class LongCatConfig:
         """LCB:17-29."""
         h = int(2 * int(self.hidden_size * self.mlp_ratio) / 3)
         return 256 * ((h + 255) // 256)
+
+
+def expected_state_dict(cfg: LongCatConfig) -> Dict[str, Tuple[int, ...]]:
+    """{reference parameter name: shape} of everything load_state_dict reads = the state dict of the reference module
+    (LCD:159-189, LCB, LCA) for this configuration.  Host only: from_pretrained checks a checkpoint's header against it before
+    anything is uploaded, the checkpoint audit reports against it."""
+    C, Ct, Hd = cfg.hidden_size, cfg.adaln_tembed_dim, cfg.ffn_hidden
+    D = C // cfg.num_heads
+    E: Dict[str, Tuple[int, ...]] = {"x_embedder.proj.weight": (C, cfg.in_channels) + tuple(cfg.patch_size), "x_embedder.proj.bias": (C,)}
+
+    def lin(name, o, i, bias=True):
+        E[name + ".weight"] = (o, i)
+        if bias:
+            E[name + ".bias"] = (o,)
+
+    lin("t_embedder.mlp.0", Ct, cfg.frequency_embedding_size)
+    lin("t_embedder.mlp.2", Ct, Ct)
+    lin("y_embedder.y_proj.0", C, cfg.caption_channels)
+    lin("y_embedder.y_proj.2", C, C)
+    lin("final_layer.linear", int(np.prod(cfg.patch_size)) * cfg.out_channels, C)
+    lin("final_layer.adaLN_modulation.1", 2 * C, Ct)
+    for i in range(cfg.depth):
+        p = f"blocks.{i}."
+        lin(p + "adaLN_modulation.1", 6 * C, Ct)
+        E[p + "pre_crs_attn_norm.weight"] = E[p + "pre_crs_attn_norm.bias"] = (C,)
+        for n, o in (("attn.qkv", 3 * C), ("attn.proj", C), ("cross_attn.q_linear", C), ("cross_attn.kv_linear", 2 * C), ("cross_attn.proj", C)):
+            lin(p + n, o, C)
+        for n in ("attn.q_norm", "attn.k_norm", "cross_attn.q_norm", "cross_attn.k_norm"):
+            E[p + n + ".weight"] = (D,)
+        lin(p + "ffn.w1", Hd, C, bias=False)
+        lin(p + "ffn.w2", C, Hd, bias=False)
+        lin(p + "ffn.w3", Hd, C, bias=False)
+    return E
+
+
+# config.json of the reference class (a diffusers ConfigMixin file, LCD:129-151): what goes into LongCatConfig, what goes to the
+# constructor, and what is accepted and dropped (the attention back-ends are this engine's kernels; sequence parallelism is `comm`)
+_CONFIG_FIELDS = ("in_channels", "out_channels", "hidden_size", "depth", "num_heads", "caption_channels", "mlp_ratio", "adaln_tembed_dim",
+                  "frequency_embedding_size", "patch_size", "text_tokens_zero_pad")
+_CONFIG_IGNORED = ("enable_flashattn2", "enable_flashattn3", "enable_xformers", "cp_split_hw")
+
+
+def config_from_dict(c: dict):
+    """-> (LongCatConfig, constructor keywords {enable_bsa, bsa_params}, [keys that are neither known nor ignored]).  ValueError for
+    a `_class_name` of another class (someone pointing the loader at a Wan `transformer/` folder)."""
+    name = c.get("_class_name")
+    if name is not None and name != "LongCatVideoTransformer3DModel":
+        raise ValueError(f"config.json is of class {name!r}, not LongCatVideoTransformer3DModel")
+    kw = {k: c[k] for k in _CONFIG_FIELDS if k in c}
+    if "patch_size" in kw:
+        kw["patch_size"] = tuple(int(v) for v in kw["patch_size"])
+    if "text_tokens_zero_pad" in kw:
+        kw["text_tokens_zero_pad"] = bool(kw["text_tokens_zero_pad"])
+    ctor = dict(enable_bsa=bool(c.get("enable_bsa", False)), bsa_params=c.get("bsa_params") or None)
+    unknown = [k for k in c if k not in _CONFIG_FIELDS and k not in _CONFIG_IGNORED and k not in ("enable_bsa", "bsa_params")
+               and not k.startswith("_")]
+    return LongCatConfig(**kw), ctor, unknown
 
 
 def timestep_embedding(ts, dim: int, max_period: float = 10000.0) -> torch.Tensor:
@@ -386,10 +447,15 @@ class LongCatVideoTransformer3DModel:
     def load_state_dict(self, sd: Dict[str, torch.Tensor]):
         """Reference-keyed state dict (any dtype / device) -> device tensors: matrices bf16, vectors fp32; the AdaLN projections of
         all blocks stacked into one matrix, w1 | w3 fused."""
-        cfg, dev = self.cfg, self.device
-        W = {}
+        dev = self.device
         mat = lambda k: sd[k].to(device=dev, dtype=torch.bfloat16).contiguous()  # noqa: E731
         vec = lambda k: sd[k].to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+        return self._assemble(mat, vec)
+
+    def _assemble(self, mat, vec):
+        """The fused storage from two readers of a reference key: mat -> bf16 device matrix, vec -> fp32 device vector."""
+        cfg = self.cfg
+        W = {}
         W["patch.w"] = mat("x_embedder.proj.weight").reshape(cfg.hidden_size, -1).contiguous()
         W["patch.b"] = vec("x_embedder.proj.bias")
         for n in ("t_embedder.mlp.0", "t_embedder.mlp.2", "y_embedder.y_proj.0", "y_embedder.y_proj.2", "final_layer.linear",
@@ -408,6 +474,51 @@ class LongCatVideoTransformer3DModel:
             W[p + "ffn.w2"] = mat(p + "ffn.w2.weight")
         self.w = W
         return self
+
+    @classmethod
+    def from_pretrained(cls, path: str, device="cuda:0", comm=None, subfolder: str = "dit", linear_precision: str = "bf16",
+                        strict: bool = True):
+        """`LongCatVideoTransformer3DModel.from_pretrained(checkpoint_dir, subfolder="dit", torch_dtype=torch.bfloat16)`
+        (run_longcat_worldforge_single.py:207) from a local folder: `<path>/<subfolder>/config.json` (config_from_dict; an unknown key
+        is ignored with one UserWarning naming it) + one safetensors file or an index with shards (checkpoint.load_dir).
+
+        Before anything is uploaded the files' headers are checked against expected_state_dict(cfg): missing keys are a KeyError,
+        keys the model does not consume a ValueError (a warning with strict=False), a wrong shape a ValueError naming key, found and
+        expected.  EVERY tensor is first rounded to bf16, whatever the file's dtype -- what torch_dtype=torch.bfloat16 does to every
+        parameter of the reference module -- and then stored as load_state_dict stores it (matrices bf16, vectors fp32 holding the
+        bf16 values).  load_state_dict itself keeps an fp32 checkpoint's vectors unrounded; this loader must not.  The tensors go from
+        the memory map to the device one at a time: no second host copy of the checkpoint is made."""
+        import json
+        import warnings
+        from . import checkpoint
+        folder = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
+        cj = os.path.join(folder, "config.json")
+        if not os.path.exists(cj):
+            raise FileNotFoundError(f"{folder}: no config.json")
+        with open(cj) as f:
+            cfg, ctor, unknown = config_from_dict(json.load(f))
+        for k in unknown:
+            warnings.warn(f"{cj}: key {k!r} is not a field of LongCatVideoTransformer3DModel and is ignored", UserWarning, stacklevel=2)
+        found, info = checkpoint.dir_header(folder)
+        if info["missing_shards"]:
+            raise FileNotFoundError(f"{folder}: shards named by {info['index']} are missing: {info['missing_shards']}")
+        missing, unexpected, wrong = checkpoint.compare_header(found, expected_state_dict(cfg))
+        if missing:
+            raise KeyError(f"{folder}: {len(missing)} parameters of the model are not in the checkpoint: {missing[:5]}")
+        if wrong:
+            w = wrong[0]
+            raise ValueError(f"{folder}: {len(wrong)} parameters have the wrong shape: {w['key']} is {w['found']}, expected {w['expected']}")
+        if unexpected:
+            msg = f"{folder}: {len(unexpected)} checkpoint tensors are not consumed by the model: {unexpected[:5]}"
+            if strict:
+                raise ValueError(msg)
+            warnings.warn(msg, UserWarning, stacklevel=2)
+        model = cls(cfg, device, comm=comm, linear_precision=linear_precision, **ctor)
+        sd = checkpoint.load_dir(folder)  # memory-mapped: a tensor's bytes are read when it is converted below
+        dev, bf = model.device, torch.bfloat16
+        mat = lambda k: sd[k].to(bf).to(dev).contiguous()  # noqa: E731
+        vec = lambda k: sd[k].to(bf).to(dev).to(torch.float32).contiguous()  # noqa: E731
+        return model._assemble(mat, vec)
 
     def init_random(self, seed: int = 0):
         """Synthetic weights of the right shapes, generated on the device (there are no checkpoints offline)."""

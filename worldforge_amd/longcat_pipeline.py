@@ -32,6 +32,26 @@ class LongCatVideoPipeline:
         self._num_distill_sample_steps = 50
         self._guidance_scale = 1.0
 
+    @classmethod
+    def from_pretrained(cls, path: str, device: Union[str, torch.device] = "cuda:0", vae_precision: str = "bf16", dit_precision: str = "bf16",
+                        flow_backend: str = "farneback", components: Optional[dict] = None):
+        """The three modules of run_longcat_worldforge_single.py:205-207 from one checkpoint folder: `vae/` as a bf16 module
+        (AutoencoderKLWan.from_pretrained(..., torch_dtype=torch.bfloat16)), `scheduler/` and `dit/`.  components: any of "vae",
+        "scheduler", "dit" to use instead of loading it.  The tokenizer and the UMT5 text encoder are not part of this pipeline (see
+        the module docstring): longcat_infer runs them once and frees them."""
+        from .longcat_dit import LongCatVideoTransformer3DModel
+        from .longcat_scheduler import FlowMatchEulerDiscreteScheduler
+        from .vae import AutoencoderKLWan
+        given = dict(components or {})
+        unknown = set(given) - {"vae", "scheduler", "dit"}
+        if unknown:
+            raise ValueError(f"components may hold 'vae', 'scheduler', 'dit', not {sorted(unknown)}")
+        vae = given["vae"] if "vae" in given else AutoencoderKLWan.from_pretrained(path, device=device, precision=vae_precision,
+                                                                                   torch_dtype=torch.bfloat16)
+        scheduler = given["scheduler"] if "scheduler" in given else FlowMatchEulerDiscreteScheduler.from_pretrained(path, flow_backend=flow_backend)
+        dit = given["dit"] if "dit" in given else LongCatVideoTransformer3DModel.from_pretrained(path, device=device, linear_precision=dit_precision)
+        return cls(vae, scheduler, dit, device=device)
+
     @property
     def guidance_scale(self):
         return self._guidance_scale

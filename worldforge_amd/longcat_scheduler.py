@@ -121,6 +121,24 @@ class FlowMatchEulerDiscreteScheduler:
         self.is_resampling = False
         self._channel_selector = None
 
+    @classmethod
+    def from_config(cls, config, **kw):
+        """A `scheduler_config.json` dictionary (or a namespace) -> the constructor; `_class_name`, `_diffusers_version` and every key
+        the constructor does not name fall into its **unused.  A configuration that is not built raises NotImplementedError there."""
+        cfg = dict(vars(config)) if isinstance(config, SimpleNamespace) else dict(config)
+        cfg.update(kw)
+        return cls(**cfg)
+
+    @classmethod
+    def from_pretrained(cls, path: str, subfolder: str = "scheduler", **kw):
+        """`FlowMatchEulerDiscreteScheduler.from_pretrained(checkpoint_dir, subfolder="scheduler")`
+        (run_longcat_worldforge_single.py:206) from a local folder."""
+        import json
+        import os
+        folder = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
+        with open(os.path.join(folder, "scheduler_config.json")) as f:
+            return cls.from_config(json.load(f), **kw)
+
     @property
     def shift(self):
         return self._shift
