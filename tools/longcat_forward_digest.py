@@ -1,0 +1,336 @@
+"""Digest of every way the LongCat DiT forward can run: for comparing two checkouts bit for bit and launch for launch.
+
+    python tools/longcat_forward_digest.py [--only PREFIX] [--dump DIR] > digest.txt
+
+One seeded random model of the multirank tests' size runs each path on a small grid; per case (and per simulated rank) one line:
+
+    <case> out=<sha256> calls=<n> launches=<sha256> trace=<sha256>
+
+out: every output tensor's bytes (the velocity; a cache's K / V^T / bound / pooled means) and the block selections where there are any.
+The launch trace is taken by a recording proxy in place of the loaded library object of `_ffi`: every call to libwf_hip.so is noted with its
+name, its scalar arguments as given and every pointer argument replaced by the ordinal of its first appearance in the trace.  `trace` is
+the hash of that, `launches` the hash of the same lines without the pointers: the ordinals say which calls share a buffer, and with it
+where PyTorch's allocator handed a freed temporary's block out again, which need not repeat from run to run.  Two checkouts whose `out`,
+`calls` and `launches` agree and whose `trace` differs issue the same kernels on the same values, with a temporary of another lifetime;
+--dump writes the full traces (one file per case) to find it with diff.
+
+Run it twice on one checkout first: what is not stable from run to run there cannot be compared between checkouts.  The digests pin a
+build's kernel rounding, not the model's contract: they are compared, never committed.  Uses only the model's public methods."""
+import argparse
+import ctypes
+import hashlib
+import os
+import sys
+import threading
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from tests.fakes import SimComm  # noqa: E402
+from worldforge_amd import _ffi  # noqa: E402
+from worldforge_amd.longcat_dit import LongCatConfig, LongCatVideoTransformer3DModel  # noqa: E402
+
+DEV = torch.device("cuda:0")
+BF = torch.bfloat16
+KW = dict(hidden_size=256, num_heads=2, caption_channels=64, adaln_tembed_dim=64)
+_TLS = threading.local()
+
+
+class _Recorder:
+    """Stands where `_ffi` keeps the loaded library: attribute access hands out the real entry point wrapped in a note-taker."""
+
+    def __init__(self, dll, protos):
+        self._dll, self._protos, self._fns = dll, protos, {}
+
+    def __getattr__(self, name):
+        fn = self._fns.get(name)
+        if fn is None:
+            real = getattr(self._dll, name)
+            argtypes = self._protos[name][1] if name in self._protos else None
+
+            def fn(*args, _real=real, _name=name, _types=argtypes):
+                trace = getattr(_TLS, "trace", None)
+                if trace is not None:
+                    trace.append((_name, _types, args))
+                return _real(*args)
+
+            self._fns[name] = fn
+        return fn
+
+
+def _install():
+    dll = _ffi.lib()
+    if not isinstance(dll, _Recorder):
+        _ffi._LIB._dll = _Recorder(dll, _ffi._LIB.protos)
+
+
+def _render(trace):
+    """-> (lines with pointer ordinals, lines without pointers)."""
+    seen, full, bare = {}, [], []
+    for name, types, args in trace:
+        a_full, a_bare = [], []
+        for j, a in enumerate(args):
+            is_ptr = types is not None and j < len(types) and types[j] in (ctypes.c_void_p, ctypes.c_char_p)
+            if is_ptr and not isinstance(a, (bytes, ctypes.Array)):
+                a_full.append("null" if not a else "p%d" % seen.setdefault(int(a), len(seen)))
+            elif isinstance(a, ctypes.Array):
+                a_full.append(repr(list(a)))
+                a_bare.append(a_full[-1])
+            else:
+                a_full.append(repr(a))
+                a_bare.append(a_full[-1])
+        full.append(f"{name}({', '.join(a_full)})")
+        bare.append(f"{name}({', '.join(a_bare)})")
+    return full, bare
+
+
+def _hash_into(h, obj):
+    if obj is None:
+        h.update(b"<none>")
+    elif torch.is_tensor(obj):
+        t = obj.detach().contiguous().cpu()
+        h.update(f"{t.dtype}{tuple(t.shape)}".encode())
+        h.update(t.view(torch.uint8).numpy().tobytes())
+    elif isinstance(obj, (list, tuple)):
+        h.update(f"[{len(obj)}".encode())
+        for o in obj:
+            _hash_into(h, o)
+    elif hasattr(obj, "cpu"):  # a selection as the fused kernels leave it (bsa.SelectionMask / SelectionMaskVar): its index form
+        _hash_into(h, obj.cpu())
+    else:
+        h.update(repr(obj).encode())
+
+
+def _sha(obj):
+    h = hashlib.sha256()
+    _hash_into(h, obj)
+    return h.hexdigest()[:32]
+
+
+def _rand(shape, seed):
+    return torch.randn(shape, generator=torch.Generator().manual_seed(seed))
+
+
+def _traced(fn):
+    """fn() with this thread's library calls recorded -> (what fn returned, trace)."""
+    _TLS.trace = []
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+        return out, _TLS.trace
+    finally:
+        _TLS.trace = None
+
+
+def _run_ranks(P, fn):
+    """tests/test_gpu_multirank.py `_run_ranks`: P simulated ranks as threads of this process; each rank's calls are traced apart."""
+    shared = {"slots": [None] * P, "bar": threading.Barrier(P)}
+    res, errs = [None] * P, []
+
+    def worker(r):
+        try:
+            res[r] = _traced(lambda: fn(SimComm(P, r, shared)))
+        except Exception as e:
+            errs.append(e)
+            shared["bar"].abort()
+
+    th = [threading.Thread(target=worker, args=(r,)) for r in range(P)]
+    [t.start() for t in th]
+    [t.join() for t in th]
+    if errs:
+        raise errs[0]
+    return res
+
+
+def _model(depth=2, seed=5, **kw):
+    return LongCatVideoTransformer3DModel(LongCatConfig(depth=depth, **KW), DEV, **kw).init_random(seed)
+
+
+def _inputs(T, Hh, Ww, ncl, n_cap=30, t=500.0):
+    x = _rand((16, T, Hh, Ww), 60).to(BF).to(DEV)
+    cap = _rand((n_cap, 64), 61).to(BF).to(DEV)
+    mask = torch.zeros(n_cap, dtype=torch.int64)
+    mask[:21] = 1
+    return x, cap, mask, [0.0] * ncl + [t] * (T - ncl)
+
+
+def _bsa_params(chunk=(4, 4, 8), **kw):
+    return dict(dict(sparsity=0.5, chunk_3d_shape_q=list(chunk), chunk_3d_shape_k=list(chunk)), **kw)
+
+
+# ---- the cases: name -> callable returning [(suffix, outputs, trace)] -------------------------------------------------------------------
+CASES = {}
+
+
+def case(name):
+    def deco(fn):
+        CASES[name] = fn
+        return fn
+    return deco
+
+
+def _single(fn):
+    out, trace = _traced(fn)
+    return [("", out, trace)]
+
+
+def _dense(ncl, masked=True, zero_pad=False, **attrs):
+    def run():
+        cfg = LongCatConfig(depth=2, text_tokens_zero_pad=zero_pad, **KW)
+        m = LongCatVideoTransformer3DModel(cfg, DEV).init_random(5)
+        for k, v in attrs.items():
+            setattr(m, k, v)
+        x, cap, mask, ts = _inputs(3, 16, 20, ncl)
+        return _single(lambda: m.forward_tokens(x, ts, cap, mask if masked else None, ncl))
+    return run
+
+
+CASES["dense.ncl0.nomask"] = _dense(0, masked=False)
+CASES["dense.ncl0.mask"] = _dense(0)
+CASES["dense.ncl1.mask"] = _dense(1)
+CASES["dense.ncl1.track_max"] = _dense(1, attn_track_max=True)
+CASES["dense.ncl1.no_prescale"] = _dense(1, attn_prescale=False)
+CASES["dense.ncl1.zero_pad"] = _dense(1, zero_pad=True)
+
+
+def _ranks(P, thw, exchange, seed=5, **model_kw):
+    def run():
+        m0 = _model(seed=seed, **model_kw)
+        ncl = 4 if model_kw.get("enable_bsa") else 1
+        x, cap, mask, ts = _inputs(*thw, ncl)
+
+        def rank_fn(comm):
+            m = LongCatVideoTransformer3DModel(m0.cfg, DEV, comm=comm, **model_kw)
+            m.w = m0.w
+            if exchange is not None:
+                m.exchange_mode, m.exchange_chunks = exchange
+            out = m.forward_tokens(x, ts, cap, None if model_kw.get("enable_bsa") else mask, ncl).clone()
+            return out, m.last_bsa_indices
+
+        return [(f".rank{r}", out, trace) for r, (out, trace) in enumerate(_run_ranks(P, rank_fn))]
+    return run
+
+
+for _P, _thw in ((2, (3, 16, 20)), (3, (5, 16, 24))):
+    for _ex in (("gather", 1), ("chunked", 2), ("bcast", 1)):
+        CASES[f"ranks{_P}.{_ex[0]}{_ex[1]}"] = _ranks(_P, _thw, _ex)
+
+
+@case("ranks2.cfg_lockstep")
+def _cfg_lockstep():
+    m0 = _model(depth=3)
+    T, Hh, Ww, ncl = 5, 16, 24, 1
+    xs = _rand((2, 16, T, Hh, Ww), 60).to(BF).to(DEV)
+    caps = _rand((2, 1, 30, 64), 61).to(BF).to(DEV)
+    masks = torch.zeros(2, 30, dtype=torch.int64)
+    masks[0, :21] = 1
+    masks[1, :9] = 1
+    tstep = torch.tensor([[0.0] * ncl + [500.0] * (T - ncl)] * 2)
+
+    def rank_fn(comm):
+        m = LongCatVideoTransformer3DModel(m0.cfg, DEV, comm=comm)
+        m.w = m0.w
+        return m(xs, tstep, caps, masks, num_cond_latents=ncl).clone()
+
+    return [(f".rank{r}", out, trace) for r, (out, trace) in enumerate(_run_ranks(2, rank_fn))]
+
+
+def _bsa(params, env=None, ncl=4):
+    def run():
+        m = _model(seed=6, enable_bsa=True, bsa_params=params)
+        x, cap, _, ts = _inputs(8, 16, 32, ncl, n_cap=20, t=400.0)
+        old = os.environ.get("WF_BSA_TORCH_SELECT")
+        if env:
+            os.environ["WF_BSA_TORCH_SELECT"] = "1"
+        try:
+            return _single(lambda: (m.forward_tokens(x, ts, cap, None, ncl), m.last_bsa_indices))
+        finally:
+            if env:
+                os.environ.pop("WF_BSA_TORCH_SELECT")
+                if old is not None:
+                    os.environ["WF_BSA_TORCH_SELECT"] = old
+    return run
+
+
+CASES["bsa.topk.ncl4"] = _bsa(_bsa_params())
+CASES["bsa.topk.ncl0"] = _bsa(_bsa_params(), ncl=0)
+CASES["bsa.cdf"] = _bsa(_bsa_params(cdf_threshold=0.9))
+CASES["bsa.cdf_only"] = _bsa(_bsa_params(cdf_threshold=0.9, sparsity=None))
+CASES["bsa.topk.torch_select"] = _bsa(_bsa_params(), env=True)
+CASES["bsa.cdf.torch_select"] = _bsa(_bsa_params(cdf_threshold=0.9), env=True)
+CASES["bsa.blocks64"] = _bsa(_bsa_params((4, 4, 4)))
+CASES["bsa.ranks2"] = _ranks(2, (8, 16, 32), None, seed=6, enable_bsa=True, bsa_params=_bsa_params())
+
+
+def _dense_cache(track_max):
+    def run():
+        m = _model(depth=3, seed=4)
+        m.attn_track_max = track_max
+        ncl, tn = 1, 3
+        x, cap, mask, ts = _inputs(ncl + tn, 8, 12, ncl, t=812.0)
+
+        def go():
+            cache = m.cache_condition(x[:, :ncl].contiguous())
+            out = m.forward_cached(x[None, :, ncl:].contiguous(), torch.tensor([ts[ncl:]]), cap[None, None], mask[None], cache)
+            return out, cache.k, cache.vt, cache.kmax2
+
+        return _single(go)
+    return run
+
+
+CASES["cache.dense"] = _dense_cache(False)
+CASES["cache.dense.track_max"] = _dense_cache(True)
+
+
+def _block_cache(chunk, Hh, Ww, ncl, tn, **params):
+    def run():
+        m = _model(seed=6, enable_bsa=True, bsa_params=_bsa_params(chunk, **params))
+        x, cap, _, ts = _inputs(ncl + tn, Hh, Ww, ncl, n_cap=20, t=400.0)
+
+        def go():
+            cache = m.cache_condition_blocks(x[:, :ncl].contiguous())
+            out = m.forward_cached_blocks(x[None, :, ncl:].contiguous(), torch.tensor([ts[ncl:]]), cap[None, None], None, cache)
+            return out, cache.k, cache.vt, cache.kcmp, cache.bsa_indices, m.last_bsa_indices
+
+        return _single(go)
+    return run
+
+
+CASES["cache.blocks.128"] = _block_cache((4, 4, 8), 16, 32, 4, 8)
+CASES["cache.blocks.64"] = _block_cache((4, 4, 4), 16, 16, 8, 4)
+CASES["cache.blocks.cdf"] = _block_cache((4, 4, 8), 16, 32, 4, 4, cdf_threshold=0.9)
+
+
+@case("mxfp8.ncl1")
+def _mxfp8():
+    m = _model(linear_precision="mxfp8")
+    x, cap, mask, ts = _inputs(4, 8, 12, 1)
+    return _single(lambda: m.forward_tokens(x, ts, cap, mask, 1))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--only", default="", help="run the cases whose name starts with this")
+    ap.add_argument("--dump", default=None, help="folder for the full traces, one file per case")
+    args = ap.parse_args()
+    _install()
+    if args.dump:
+        os.makedirs(args.dump, exist_ok=True)
+    for name, fn in CASES.items():
+        if not name.startswith(args.only):
+            continue
+        try:
+            rows = fn()
+        except (ValueError, NotImplementedError, AssertionError) as e:  # a host-side refusal; anything else ends the run
+            print(f"{name} ERROR {type(e).__name__}: {e}", flush=True)
+            continue
+        for suffix, out, trace in rows:
+            full, bare = _render(trace)
+            print(f"{name}{suffix} out={_sha(out)} calls={len(full)} launches={_sha(bare)} trace={_sha(full)}", flush=True)
+            if args.dump:
+                with open(os.path.join(args.dump, f"{name}{suffix}.txt"), "w") as f:
+                    f.write("\n".join(full) + "\n")
+
+
+if __name__ == "__main__":
+    main()

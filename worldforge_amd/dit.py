@@ -26,6 +26,7 @@ import torch
 
 from . import _ffi, ops
 from ._ffi import WF_BF16, WF_F32, call
+from .forward_common import ForwardWorkspaces, run, wait_events
 
 EPI_BF16, EPI_BF16_GELU, EPI_F32, EPI_RESID, EPI_F32_ACC = 0, 1, 2, 3, 4
 
@@ -401,7 +402,7 @@ def expected_diffusers_state_dict(cfg: DiTConfig) -> Dict[str, tuple]:
     return out
 
 
-class WanTransformer3DModel:
+class WanTransformer3DModel(ForwardWorkspaces):
     dtype = torch.bfloat16
 
     # the per-block token GEMMs that linear_precision="mxfp8" runs in MX-fp8 (embeddings, head and the prompt-context K / V stay bf16)
@@ -582,13 +583,7 @@ class WanTransformer3DModel:
     # ------------------------------------------------------------------------------------------------------------
     # workspaces (allocated once per token count; everything stays resident in HBM)
     # ------------------------------------------------------------------------------------------------------------
-    def _buf(self, name, shape, dtype, zero=False):
-        key = (name, tuple(shape), dtype)
-        t = self._ws.get(key)
-        if t is None:
-            t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.device)
-            self._ws[key] = t
-        return t
+    _rope_fn = staticmethod(rope_tables)  # (_buf, _exchange, _rope_tables: forward_common.ForwardWorkspaces)
 
     def _context_kv(self, text: torch.Tensor, img: torch.Tensor):
         """Per-layer cross-attention K / V cache for one (text, image) context: {layer: (k, vT)} in the fused [image | text] layout.  The
@@ -611,22 +606,6 @@ class WanTransformer3DModel:
             # the tensors are held so that their storage (and hence data_ptr) cannot be recycled while the entry lives
             hit = cache[key] = {"_keep": (text, img)}
         return hit
-
-    def _exchange(self, tag: str, H: int, shard_len: int, mode: str, chunks: int):
-        """The K / V^T exchange buffers of the forward `tag` (parallel.KVExchange), allocated once per shape and mode."""
-        from .parallel import KVExchange
-        key = ("kvx" + tag, H, shard_len, mode, chunks, id(self.comm))
-        ex = self._ws.get(key)
-        if ex is None:
-            ex = self._ws[key] = KVExchange(self.comm, H, shard_len, mode, chunks, self.device)
-        return ex
-
-    def _rope_tables(self, f, h, w):
-        key = (f, h, w)
-        if key not in self._rope:
-            c, s = rope_tables(128, f, h, w)
-            self._rope[key] = (c.to(self.device), s.to(self.device))
-        return self._rope[key]
 
     # ------------------------------------------------------------------------------------------------------------
     # forward
@@ -723,8 +702,7 @@ class WanTransformer3DModel:
     def forward_tokens(self, x_in: torch.Tensor, t_value: float, text: torch.Tensor, img: torch.Tensor) -> torch.Tensor:
         """x_in [in_dim, T, h, w] bf16; text [<=512, text_dim]; img [n_img, img_dim] -> velocity [out_dim, T, h, w] f32."""
         out = [None]
-        for _ in self._forward_steps(x_in, t_value, text, img, "", out, self.exchange_mode):
-            pass
+        run(self._forward_steps(x_in, t_value, text, img, "", out, self.exchange_mode))
         return out[0]
 
     def forward_tokens_pair(self, x_in: torch.Tensor, t_value: float, text_a: torch.Tensor, text_b: torch.Tensor,
@@ -744,21 +722,13 @@ class WanTransformer3DModel:
         share = {} if self.pair_share_layer0 else None
         if not interleave:
             oa, ob = [None], [None]
-            for _ in self._forward_steps(x_in, t_value, text_a, img, "", oa, self.exchange_mode, share, "produce"):
-                pass
-            for _ in self._forward_steps(x_in, t_value, text_b, img, "", ob, self.exchange_mode, share, "consume"):
-                pass
+            run(self._forward_steps(x_in, t_value, text_a, img, "", oa, self.exchange_mode, share, "produce"))
+            run(self._forward_steps(x_in, t_value, text_b, img, "", ob, self.exchange_mode, share, "consume"))
             return oa[0], ob[0]
         oa, ob = [None], [None]
         ga = self._forward_steps(x_in, t_value, text_a, img, "", oa, "gather", share, "produce")
         gb = self._forward_steps(x_in, t_value, text_b, img, "#b", ob, "gather", share, "consume")
-        live = [ga, gb]
-        while live:
-            for gen in list(live):
-                try:
-                    next(gen)
-                except StopIteration:
-                    live.remove(gen)
+        run(ga, gb)
         return oa[0], ob[0]
 
     def _forward_steps(self, x_in, t_value, text, img, tag, result, mode="gather", share=None, role=None):
@@ -925,9 +895,7 @@ class WanTransformer3DModel:
             kv = ctx_kv.get(i) if ctx_kv is not None else None
             if ctx_shared is not None:
                 if ctx_events is not None:  # first use: the gathers were launched before layer 0
-                    for ev in ctx_events:
-                        if ev is not None:
-                            torch.cuda.current_stream().wait_event(ev)
+                    wait_events(ctx_events)
                     ctx_events = None
                 allb, P_ = ctx_shared
                 kc, vtc = (a_[i % P_, i // P_] for a_ in allb)

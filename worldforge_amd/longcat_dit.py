@@ -46,6 +46,7 @@ from . import ops
 from ._ffi import WF_BF16, WF_F32, call
 from .dit import (EPI_BF16, EPI_BF16_GELU, EPI_F32, EPI_F32_ACC, _pad64, attention, attention_exchange, gemm, head_max_norm2,
                   quantize_linears)
+from .forward_common import ForwardWorkspaces, run, wait_events
 
 
 @dataclass
@@ -196,13 +197,8 @@ _LORA_H = "___lorahyphen___"
 
 
 @dataclass(eq=False)
-class LongCatCondCache:
-    """The condition frames' self-attention keys / values of every block (LCA:149-181 `kv_cache_dict`), resident on the GPU in the
-    layout wf_attn_fwd reads, built by LongCatVideoTransformer3DModel.cache_condition.  K is normalised AND rotated: a frame's RoPE rows
-    do not depend on how many frames follow (rope_tables), so the rotation of LCA:168-172 is done once."""
-    k: torch.Tensor        # bf16 [depth, H, pad64(nc), 128], rows nc.. zero
-    vt: torch.Tensor       # bf16 [depth, H, pad64(nc) / 64, 128, 64], keys nc.. zero
-    kmax2: torch.Tensor    # f32 [depth, H]: max |k row|^2 per head over the nc cached rows (wf_head_max_norm2)
+class _CondCache:
+    """What both condition caches say about themselves: their size, and the model and weights they were built with."""
     ncl: int               # condition latent frames
     nc: int                # condition tokens = ncl * tokens per frame
     latent_hw: Tuple[int, int]
@@ -213,7 +209,17 @@ class LongCatCondCache:
 
 
 @dataclass(eq=False)
-class LongCatBlockCondCache:
+class LongCatCondCache(_CondCache):
+    """The condition frames' self-attention keys / values of every block (LCA:149-181 `kv_cache_dict`), resident on the GPU in the
+    layout wf_attn_fwd reads, built by LongCatVideoTransformer3DModel.cache_condition.  K is normalised AND rotated: a frame's RoPE rows
+    do not depend on how many frames follow (rope_tables), so the rotation of LCA:168-172 is done once."""
+    k: torch.Tensor        # bf16 [depth, H, pad64(nc), 128], rows nc.. zero
+    vt: torch.Tensor       # bf16 [depth, H, pad64(nc) / 64, 128, 64], keys nc.. zero
+    kmax2: torch.Tensor    # f32 [depth, H]: max |k row|^2 per head over the nc cached rows (wf_head_max_norm2)
+
+
+@dataclass(eq=False)
+class LongCatBlockCondCache(_CondCache):
     """The condition cache of the block-sparse refine pass (cache_condition_blocks): every tensor in 3D-BLOCK token order, in which
     the condition tokens are the first nc rows of every (condition + noise) grid (bsa_interface.py:600-604 orders by frame chunk first
     and ncl is whole chunks), so nc is whole blocks and whole 64-key tiles.  Besides K / V^T it keeps the pooled key-block means
@@ -222,16 +228,9 @@ class LongCatBlockCondCache:
     vt: torch.Tensor       # bf16 [depth, H, nc / 64, 128, 64]
     kcmp: torch.Tensor     # bf16 [depth, H, nc / block, 128]: mean of every key block
     bsa_indices: list      # per DiT block the condition-query selection of the build (what last_bsa_indices held; read by tests)
-    ncl: int
-    nc: int
-    latent_hw: Tuple[int, int]
     chunk: Tuple[int, int, int]
     sparsity: Optional[float]
     cdf_threshold: Optional[float]
-    owner: object
-    wver: int
-    loras: Tuple[str, ...]
-    linear_precision: str
 
 
 @dataclass(eq=False)
@@ -245,7 +244,30 @@ class LoRAPart:
     scale: float         # multiplier * alpha_scale
 
 
-class LongCatVideoTransformer3DModel:
+@dataclass(frozen=True, eq=False)
+class _ForwardPlan:
+    """Everything one forward derives from its arguments (LongCatVideoTransformer3DModel._plan), fixed before its first launch.  Counts
+    of the whole sequence and of this rank's rows have names of their own: without `comm` they differ by the cached keys only."""
+    tag: str                                    # separates the workspaces of concurrent forwards
+    T: int; Hh: int; Ww: int; tpf: int          # noqa: E702  this forward's latent frames, their size, tokens per frame
+    L_tok: int                                  # this forward's tokens, over all ranks
+    L_all: int; nc_all: int                     # noqa: E702  the keys a noise / a condition query sees: kc + L_tok / the condition tokens
+    L: int; nc: int; lo: int                    # noqa: E702  this rank's rows, its condition rows (the first), its first row's global index
+    kc: int; fc: int                            # noqa: E702  cached condition keys / frames IN FRONT of this forward's rows (0 without "use")
+    Sp: int                                     # key rows of a shard = of a K workspace (whole 64-key tiles)
+    blk: int                                    # tokens per attention block (64 in the dense paths)
+    cos: torch.Tensor; sin: torch.Tensor        # noqa: E702  RoPE tables of this rank's rows (in block order under block-sparse attention)
+    gidx: object; perm: object; pos: object     # noqa: E702  block order: frame index per row, the permutation, its inverse; else None
+    shard: object                               # parallel.ShardPlan, None without `comm`
+    use_bsa: bool
+    build: bool; cached: bool; cache: object    # noqa: E702  vc = ("build", cache) / ("use", cache)
+    prescale: bool; use_bounds: bool            # noqa: E702
+    scale: float; q_scale: float; sa_scale: float  # noqa: E702  1 / sqrt(head_dim); what the query producer folds in / the kernel is told
+    exchange: Optional[str]                     # the effective mode of the K / V^T exchange; None: this forward has none
+    sparsity: Optional[float]; cdf_thr: Optional[float]; fused_sel: bool  # noqa: E702  the block selection rule (bsa_params, WF_BSA_TORCH_SELECT)
+
+
+class LongCatVideoTransformer3DModel(ForwardWorkspaces):
     dtype = torch.bfloat16
 
     # the per-block token GEMMs that linear_precision="mxfp8" runs in MX-fp8 (embeddings, AdaLN, final layer and the caption K / V stay bf16)
@@ -556,20 +578,7 @@ class LongCatVideoTransformer3DModel:
         return sum(t.numel() * t.element_size() for t in self.w.values())
 
     # ------------------------------------------------------------------------------------------------------------
-    def _buf(self, name, shape, dtype, zero=False):
-        key = (name, tuple(shape), dtype)
-        t = self._ws.get(key)
-        if t is None:
-            t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.device)
-            self._ws[key] = t
-        return t
-
-    def _rope_tables(self, f, h, w):
-        key = (f, h, w)
-        if key not in self._rope:
-            c, s = rope_tables(128, f, h, w)
-            self._rope[key] = (c.to(self.device), s.to(self.device))
-        return self._rope[key]
+    _rope_fn = staticmethod(rope_tables)  # (_buf, _exchange, _rope_tables: forward_common.ForwardWorkspaces)
 
     def _act(self, a, out_dtype, mode):
         out = torch.empty(a.shape, dtype=out_dtype, device=a.device)
@@ -630,21 +639,12 @@ class LongCatVideoTransformer3DModel:
     attn_prescale = True
     attn_track_max = False
 
-    def _exchange(self, tag: str, H: int, shard_len: int, mode: str, chunks: int):
-        from .parallel import KVExchange
-        key = ("kvx" + tag, H, shard_len, mode, chunks, id(self.comm))
-        ex = self._ws.get(key)
-        if ex is None:
-            ex = self._ws[key] = KVExchange(self.comm, H, shard_len, mode, chunks, self.device)
-        return ex
-
     def forward_tokens(self, x_in: torch.Tensor, timesteps, caption: torch.Tensor, caption_mask: Optional[torch.Tensor] = None,
                        num_cond_latents: int = 0) -> torch.Tensor:
         """One sample.  x_in [16, T, Hh, Ww] bf16; timesteps: T host floats; caption [N, caption_channels] bf16; caption_mask [N]
         host / device ints (0 = padding) or None -> velocity [16, T, Hh, Ww] fp32  (LCD:279-366)."""
         out = [None]
-        for _ in self._forward_steps(x_in, timesteps, caption, caption_mask, num_cond_latents, "", out, self.exchange_mode):
-            pass
+        run(self._forward_steps(x_in, timesteps, caption, caption_mask, num_cond_latents, "", out, self.exchange_mode))
         return out[0]
 
     def forward_tokens_pair(self, sample_a, sample_b, num_cond_latents: int = 0):
@@ -655,15 +655,8 @@ class LongCatVideoTransformer3DModel:
         versa (the scheme of dit.WanTransformer3DModel.forward_tokens_pair).  Each sample issues exactly the kernels of forward_tokens in
         exchange mode "gather" on its own buffers: bit-identical to two sequential calls."""
         oa, ob = [None], [None]
-        ga = self._forward_steps(*sample_a, num_cond_latents, "", oa, "gather")
-        gb = self._forward_steps(*sample_b, num_cond_latents, "#b", ob, "gather")
-        live = [ga, gb]
-        while live:
-            for gen in list(live):
-                try:
-                    next(gen)
-                except StopIteration:
-                    live.remove(gen)
+        run(self._forward_steps(*sample_a, num_cond_latents, "", oa, "gather"),
+                     self._forward_steps(*sample_b, num_cond_latents, "#b", ob, "gather"))
         return oa[0], ob[0]
 
     def _forward_steps(self, x_in, timesteps, caption, caption_mask, num_cond_latents, tag, result, mode="gather", vc=None):
@@ -683,97 +676,164 @@ class LongCatVideoTransformer3DModel:
         copied to the front of a working K / V^T pair, this step's keys are appended behind them, and everything else runs on the
         noise rows.  With block-sparse attention on (a LongCatBlockCondCache) both modes run in block order: the build also keeps
         the pooled key-block means and its selection, a step appends its own means behind the cached ones (wf_lc_mean_pool_blocks_at)
-        and scores / selects / attends for the noise query blocks only, over all (nc + L) / block key blocks."""
-        cfg, W, dev = self.cfg, self._wl, self.device
-        bf, f32 = torch.bfloat16, torch.float32
+        and scores / selects / attends for the noise query blocks only, over all (nc + L) / block key blocks.
+
+        The stages are methods on one plan and one set of workspaces; self-attention is one method per path (_sa_*)."""
+        pl = self._plan(x_in, timesteps, num_cond_latents, tag, mode, vc)
+        W, C, tpf = self._wl, self.cfg.hidden_size, pl.tpf
+        emb = self._embed(pl, x_in, timesteps, caption, caption_mask)
+        ws = self._workspaces(pl, emb.n_txt)
+        ctx = self._shared_caption_kv(pl, ws, emb)
+        x, ada, ald = emb.x, emb.ada, emb.ald
+        if pl.use_bsa:
+            self.last_bsa_indices = []
+        for i in range(self.cfg.depth):
+            p = f"blocks.{i}."
+            m = ada[:, i * 6 * C:(i + 1) * 6 * C]
+            shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp = (m[:, j * C:(j + 1) * C] for j in range(6))
+            last_of_build = pl.build and i == self.cfg.depth - 1
+            # ---- self-attention (LCD:91-104, LCA:105-145) ----
+            self._ln(x, scale_msa, shift_msa, ald, tpf, True, ws.hbuf, row0=pl.lo, gidx=pl.gidx)
+            gemm(ws.hbuf, W[p + "attn.qkv.w"], W[p + "attn.qkv.b"], ws.qkv, EPI_BF16)
+            if pl.use_bsa:
+                self._sa_block_sparse(pl, ws, i)
+                if last_of_build:
+                    return  # the block-sparse build stops AFTER its last attention: it keeps that block's selection too
+            elif pl.exchange is not None:
+                yield from self._sa_dense_exchange(pl, ws, i)
+            elif pl.cache is not None:
+                self._sa_dense_cached(pl, ws, i, attend=not last_of_build)
+                if last_of_build:
+                    # the dense build stops BEFORE its last attention: the last block's keys are in the cache, nothing reads the
+                    # condition stream behind them
+                    return
+            else:
+                self._sa_dense_local(pl, ws, i)
+            gemm(ws.ao, W[p + "attn.proj.w"], W[p + "attn.proj.b"], ws.ys, EPI_BF16)
+            self._resid(x, ws.ys, gate_msa, ald, tpf, row0=pl.lo, gidx=pl.gidx)
+            if not pl.build and pl.L - pl.nc > 0:  # (a build has condition rows only: LCA:127-131 skip_crs_attn)
+                self._cross_attention(pl, ws, emb, ctx, i)
+            # ---- SwiGLU FFN (LCD:113-120, LCB:36-37) ----
+            self._ln(x, scale_mlp, shift_mlp, ald, tpf, True, ws.hbuf, row0=pl.lo, gidx=pl.gidx)
+            gemm(ws.hbuf, W[p + "ffn.w13"], None, ws.ffh, EPI_BF16)
+            call("wf_lc_swiglu", ws.ffh.data_ptr(), ws.ffh.stride(0), ws.ffg.data_ptr(), pl.L, self.cfg.ffn_hidden, ops.stream())
+            gemm(ws.ffg, W[p + "ffn.w2"], None, ws.ys, EPI_BF16)
+            self._resid(x, ws.ys, gate_mlp, ald, tpf, row0=pl.lo, gidx=pl.gidx)
+        assert not pl.build
+        result[0] = self._final_layer(pl, ws, emb)
+
+    def _block_order(self, T, fc, kc, h2, w2, num_cond_latents, cos, sin):
+        """The refine pass keeps the WHOLE network in 3D-block token order (bsa_interface.py:600-604): every row-wise op is order
+        agnostic once the per-frame AdaLN kernels take a per-row frame index, the RoPE tables are permuted once, and the velocity rows
+        are put back in (T, H, W) order at the end -- no per-layer permutes, and contiguous runs of blocks are the shards of the
+        sequence-parallel job.  The first nc rows of the block order are the condition tokens.
+        cos / sin: the (fc + T) grid's tables -> (block tokens, permuted cos, sin, per-row frame index, permutation, its inverse)."""
+        from . import bsa
+        dev, tpf = self.device, h2 * w2
+        cq, ck = self.bsa_params["chunk_3d_shape_q"], self.bsa_params["chunk_3d_shape_k"]
+        if list(cq) != list(ck):
+            raise NotImplementedError("different query / key block shapes")
+        ncl = int(num_cond_latents or 0)
+        if ncl % cq[0] or (T - ncl) % cq[0]:
+            raise ValueError(f"block-sparse attention needs the condition ({ncl}) and noise ({T - ncl}) latent frames to be "
+                             f"multiples of {cq[0]} (the reference pads them: pipeline_longcat_video.py:1417-1419)")
+        blk = cq[0] * cq[1] * cq[2]
+        if kc:
+            # a cached step: its rows are rows kc.. of the (fc + T) grid's block order -- that grid's permuted RoPE tables (sliced at kc
+            # by the plan), and its permutation / frame indices / inverse permutation restricted to those rows, counted from the first
+            # noise token / frame
+            key = ("blk_vc", fc, T, h2, w2, tuple(cq))
+            if key not in self._rope:
+                pf, qf = bsa.block_permutation(fc + T, h2, w2, cq, dev)
+                rows = pf.long()
+                self._rope[key] = (cos[rows].contiguous(), sin[rows].contiguous(), (pf[kc:] // tpf - fc).to(torch.int32).contiguous(),
+                                   (pf[kc:] - kc).contiguous(), (qf[kc:] - kc).contiguous())
+            return (blk,) + tuple(self._rope[key])
+        perm, pos = bsa.block_permutation(T, h2, w2, cq, dev)
+        key = ("blk", T, h2, w2, tuple(cq))
+        if key not in self._rope:
+            rows = perm.long()
+            self._rope[key] = (cos[rows].contiguous(), sin[rows].contiguous(), (perm // tpf).to(torch.int32).contiguous())
+        return (blk,) + tuple(self._rope[key]) + (perm, pos)
+
+    def _plan(self, x_in, timesteps, num_cond_latents, tag, mode, vc) -> _ForwardPlan:
+        """Everything a forward derives from its arguments, before the first launch."""
+        cfg, comm = self.cfg, self.comm
         Cin, T, Hh, Ww = x_in.shape
         assert Cin == cfg.in_channels and len(timesteps) == T
-        C, H, Hd, Ct = cfg.hidden_size, cfg.num_heads, cfg.ffn_hidden, cfg.adaln_tembed_dim
         h2, w2 = Hh // 2, Ww // 2
         tpf = h2 * w2
         build = vc is not None and vc[0] == "build"
+        cached = vc is not None and not build
         cache = vc[1] if vc is not None else None
-        # kc / fc: the cached condition keys / frames IN FRONT of this forward's rows (0 unless vc = "use")
-        kc, fc = (cache.nc, cache.ncl) if vc is not None and not build else (0, 0)
-        L, Lp = T * tpf, _pad64(kc + T * tpf)
-        nc = L if build else int(num_cond_latents or 0) * tpf
-        assert 0 <= nc < L or build
+        kc, fc = (cache.nc, cache.ncl) if cached else (0, 0)
+        L_tok = T * tpf
+        nc_all = L_tok if build else int(num_cond_latents or 0) * tpf
+        assert 0 <= nc_all < L_tok or build
         scale = 1.0 / math.sqrt(128.0)
-        cos, sin = self._rope_tables(fc + T, h2, w2)
-        _buf = lambda name, shape, dtype, zero=False: self._buf(name + tag, shape, dtype, zero)  # noqa: E731
-        comm = self.comm
+        cos_thw, sin_thw = self._rope_tables(fc + T, h2, w2)
         use_bsa = self._bsa and fc + T > 1  # LCA:57: "bsa will not be used in image training / sampling"
-        gidx = perm = pos = None
-        blk = 64
-        if use_bsa:
-            # The refine pass keeps the WHOLE network in 3D-block token order (bsa_interface.py:600-604): every row-wise op is order
-            # agnostic once the per-frame AdaLN kernels take a per-row frame index, the RoPE tables are permuted once, and the
-            # velocity rows are put back in (T, H, W) order at the end -- no per-layer permutes, and contiguous runs of blocks are the
-            # shards of the sequence-parallel job.  The first nc rows of the block order are the condition tokens.
-            from . import bsa
-            cq, ck = self.bsa_params["chunk_3d_shape_q"], self.bsa_params["chunk_3d_shape_k"]
-            if list(cq) != list(ck):
-                raise NotImplementedError("different query / key block shapes")
-            ncl = int(num_cond_latents or 0)
-            if ncl % cq[0] or (T - ncl) % cq[0]:
-                raise ValueError(f"block-sparse attention needs the condition ({ncl}) and noise ({T - ncl}) latent frames to be "
-                                 f"multiples of {cq[0]} (the reference pads them: pipeline_longcat_video.py:1417-1419)")
-            blk = cq[0] * cq[1] * cq[2]
-            if kc:
-                # a cached step: its rows are rows kc.. of the (fc + T) grid's block order -- that grid's permuted RoPE tables (`cos` /
-                # `sin` are that grid's; sliced at kc below), and its permutation / frame indices / inverse permutation restricted to
-                # those rows, counted from the first noise token / frame
-                key = ("blk_vc", fc, T, h2, w2, tuple(cq))
-                if key not in self._rope:
-                    pf, qf = bsa.block_permutation(fc + T, h2, w2, cq, dev)
-                    pl = pf.long()
-                    self._rope[key] = (cos[pl].contiguous(), sin[pl].contiguous(), (pf[kc:] // tpf - fc).to(torch.int32).contiguous(),
-                                       (pf[kc:] - kc).contiguous(), (qf[kc:] - kc).contiguous())
-                cos, sin, gidx, perm, pos = self._rope[key]
-            else:
-                perm, pos = bsa.block_permutation(T, h2, w2, cq, dev)
-                key = ("blk", T, h2, w2, tuple(cq))
-                if key not in self._rope:
-                    pl = perm.long()
-                    self._rope[key] = (cos[pl].contiguous(), sin[pl].contiguous(), (perm // tpf).to(torch.int32).contiguous())
-                cos, sin, gidx = self._rope[key]
+        blk, cos_all, sin_all, gidx, perm, pos = (self._block_order(T, fc, kc, h2, w2, num_cond_latents, cos_thw, sin_thw) if use_bsa
+                                                  else (64, cos_thw, sin_thw, None, None, None))
+        sparsity, cdf_thr = (self.bsa_params.get("sparsity"), self.bsa_params.get("cdf_threshold")) if use_bsa else (None, None)
+        if use_bsa and sparsity is None and cdf_thr is None:
+            raise ValueError("bsa_params needs sparsity and / or cdf_threshold (bsa_interface.py:265-274)")
         if comm is not None:
-            from .parallel import ShardPlan, gather_rows, shard_plan
+            from .parallel import ShardPlan, shard_plan
             if use_bsa:  # whole 256-row query groups (two 128-token / four 64-token blocks) per rank
-                per = (L + comm.world - 1) // comm.world
-                plan = ShardPlan(L=L, P=comm.world, shard_len=(per + 255) // 256 * 256)
+                per = (L_tok + comm.world - 1) // comm.world
+                shard = ShardPlan(L=L_tok, P=comm.world, shard_len=(per + 255) // 256 * 256)
             else:
-                plan = shard_plan(L, comm.world)
-            lo, hi = plan.bounds(comm.rank)
-            Lr, Sp = hi - lo, plan.shard_len
-            if Lr <= 0:
-                raise ValueError(f"sequence-parallel plan leaves rank {comm.rank} of {comm.world} without tokens ({L} tokens in shards "
+                shard = shard_plan(L_tok, comm.world)
+            lo, hi = shard.bounds(comm.rank)
+            L, Sp = hi - lo, shard.shard_len
+            if L <= 0:
+                raise ValueError(f"sequence-parallel plan leaves rank {comm.rank} of {comm.world} without tokens ({L_tok} tokens in shards "
                                  f"of {Sp}); use fewer ranks for this size")
         else:
-            plan, lo, Lr, Sp = None, 0, L, Lp
-        ncr = min(max(nc - lo, 0), Lr)  # this rank's condition rows
-        cos, sin = cos[kc + lo:kc + lo + Lr], sin[kc + lo:kc + lo + Lr]
+            shard, lo, L, Sp = None, 0, L_tok, _pad64(kc + L_tok)
+        # dense self-attention (no block gating on Q): as in the Wan DiT (dit.py), softmax_scale * log2(e) is folded into Q by its producer and
+        # the kernel runs its exp2-domain form (softmax_scale = 0), without max tracking where the per-head norm bound allows it.  The
+        # block-sparse pass keeps the in-kernel scale: its Q also feeds the gating.
+        prescale = (not use_bsa) and bool(self.attn_prescale)
+        q_scale, sa_scale = (scale * 1.4426950408889634, 0.0) if prescale else (1.0, scale)
+        exchange = None
+        if comm is not None and not use_bsa:  # (block-sparse blocks gather K / V^T densely instead)
+            # part launches are built for the pre-scaled-Q form
+            exchange = mode if prescale and comm.world > 1 else "gather"
+        return _ForwardPlan(
+            tag=tag, T=T, Hh=Hh, Ww=Ww, tpf=tpf, L_tok=L_tok, L_all=kc + L_tok, nc_all=nc_all, L=L, nc=min(max(nc_all - lo, 0), L), lo=lo,
+            kc=kc, fc=fc, Sp=Sp, blk=blk, cos=cos_all[kc + lo:kc + lo + L], sin=sin_all[kc + lo:kc + lo + L], gidx=gidx, perm=perm, pos=pos,
+            shard=shard, use_bsa=use_bsa, build=build, cached=cached, cache=cache, prescale=prescale,
+            use_bounds=prescale and not self.attn_track_max, scale=scale, q_scale=q_scale, sa_scale=sa_scale, exchange=exchange,
+            sparsity=sparsity, cdf_thr=cdf_thr,
+            fused_sel=not os.environ.get("WF_BSA_TORCH_SELECT"))  # (the env switch keeps the torch selection paths testable)
 
-        # ---- embeddings ----
-        tok = _buf("tok", (L, Cin * 4), bf)
-        call("wf_patchify", x_in.data_ptr(), tok.data_ptr(), Cin, T, Hh, Ww, ops.stream())
-        if use_bsa:
-            tokb = _buf("tokb", (L, Cin * 4), bf)
-            call("wf_gather_rows_bf16", tok.data_ptr(), tok.stride(0), perm.data_ptr(), tokb.data_ptr(), tokb.stride(0), L, Cin * 4,
-                 ops.stream())
-            tok = tokb
-        tok = tok[lo:lo + Lr]
-        L_all, nc_all = kc + L, nc
-        L, nc = Lr, ncr  # from here on L / nc are this rank's row counts; L_all / nc_all the key counts
-        x = _buf("x", (L, C), bf)
-        gemm(tok, W["patch.w"], W["patch.b"], x, EPI_BF16)  # LCB:112 (Conv3d with kernel = stride = patch)
+    def _tagged_buf(self, pl):
+        return lambda name, shape, dtype, zero=False: self._buf(name + pl.tag, shape, dtype, zero)
+
+    def _embed(self, pl, x_in, timesteps, caption, caption_mask):
+        """Patch, timestep and caption embeddings -> (x: this rank's residual stream, ada / ald: the AdaLN parameters of all blocks and
+        their row stride, fmod: the final layer's, y / n_txt: the caption tokens); a build has no caption and no final layer."""
+        cfg, W, dev = self.cfg, self._wl, self.device
+        bf, f32 = torch.bfloat16, torch.float32
+        C, Ct, Cin, T = cfg.hidden_size, cfg.adaln_tembed_dim, cfg.in_channels, pl.T
+        _buf = self._tagged_buf(pl)
+        tok_thw = _buf("tok", (pl.L_tok, Cin * 4), bf)
+        call("wf_patchify", x_in.data_ptr(), tok_thw.data_ptr(), Cin, T, pl.Hh, pl.Ww, ops.stream())
+        tok = _buf("tokb", (pl.L_tok, Cin * 4), bf) if pl.use_bsa else tok_thw
+        if pl.use_bsa:
+            call("wf_gather_rows_bf16", tok_thw.data_ptr(), tok_thw.stride(0), pl.perm.data_ptr(), tok.data_ptr(), tok.stride(0), pl.L_tok,
+                 Cin * 4, ops.stream())
+        x = _buf("x", (pl.L, C), bf)
+        gemm(tok[pl.lo:pl.lo + pl.L], W["patch.w"], W["patch.b"], x, EPI_BF16)  # LCB:112 (Conv3d with kernel = stride = patch)
         tf = timestep_embedding(timesteps, cfg.frequency_embedding_size).to(dev)  # LCB:201-206
         t0 = self._gemm_f32(tf, W["t_embedder.mlp.0.w"], W["t_embedder.mlp.0.b"], _buf("t0", (T, Ct), f32))
         t = self._gemm_f32(self._act(t0, f32, 0), W["t_embedder.mlp.2.w"], W["t_embedder.mlp.2.b"], _buf("t", (T, Ct), f32))
         st = self._act(t, f32, 0)  # SiLU(t), shared by every adaLN_modulation (LCD:40-43, LCB:156)
         ada = self._gemm_f32(st, W["ada.w"], W["ada.b"], _buf("ada", (T, W["ada.w"].shape[0]), f32))   # (all stored blocks: a run on the first cfg.depth blocks only reads its own columns)
-        y, n_txt = None, 0
-        if not build:
+        fmod, y, n_txt = None, None, 0
+        if not pl.build:
             fmod = self._gemm_f32(st, W["final_layer.adaLN_modulation.1.w"], W["final_layer.adaLN_modulation.1.b"], _buf("fmod", (T, 2 * C), f32))
             # caption: Linear -> GELU(tanh) -> Linear (LCB:225-228), valid tokens only (LCD:319-325)
             cap = caption
@@ -789,239 +849,250 @@ class LongCatVideoTransformer3DModel:
             gemm(yh, W["y_embedder.y_proj.2.w"], W["y_embedder.y_proj.2.b"], y, EPI_BF16)
             if caption_mask is not None and cfg.text_tokens_zero_pad:
                 y[(~keep).to(dev)] = 0  # LCD:315-317
-        Ltp = _pad64(n_txt)
+        return SimpleNamespace(x=x, ada=ada, ald=ada.stride(0), fmod=fmod, y=y, n_txt=n_txt)
 
-        hbuf = _buf("h", (L, C), bf)
-        qkv = _buf("qkv", (L, 3 * C), bf)
-        qh_c = _buf("qh_c", (H, max(nc, 1), 128), bf)
-        qh_n = _buf("qh_n", (H, max(L - nc, 1), 128), bf)  # (a rank of a sequence-parallel job may hold condition rows only)
-        # dense self-attention (no block gating on Q): as in the Wan DiT (dit.py), softmax_scale * log2(e) is folded into Q by its producer and
-        # the kernel runs its exp2-domain form (softmax_scale = 0), without max tracking where the per-head norm bound allows it.  The
-        # block-sparse pass keeps the in-kernel scale: its Q also feeds the gating.
-        prescale = (not use_bsa) and bool(self.attn_prescale)
-        q_scale, sa_scale = (scale * 1.4426950408889634, 0.0) if prescale else (1.0, scale)
-        use_bounds = prescale and not self.attn_track_max
-        qm_c = _buf("qmax2_c", (H,), f32) if use_bounds else None
-        qm_n = _buf("qmax2_n", (H,), f32) if use_bounds else None
-        ex = kh = vt = km = None
-        if comm is not None and not use_bsa:
+    def _workspaces(self, pl, n_txt):
+        """Every per-block workspace of this forward, and with it who holds the self-attention keys: `ex` (the exchange slots), or
+        kh / vt / km (/ kcw, kh_all / vt_all) -- all None for a build, which writes the cache's own tensors."""
+        cfg, comm = self.cfg, self.comm
+        bf, f32 = torch.bfloat16, torch.float32
+        C, H, Hd, L, nc, Sp = cfg.hidden_size, cfg.num_heads, cfg.ffn_hidden, pl.L, pl.nc, pl.Sp
+        Ltp = _pad64(n_txt)
+        _buf = self._tagged_buf(pl)
+        ws = SimpleNamespace(ex=None, kh=None, vt=None, km=None, kcw=None, kh_all=None, vt_all=None)
+        ws.hbuf = _buf("h", (L, C), bf)
+        ws.qkv = _buf("qkv", (L, 3 * C), bf)
+        ws.qh_c = _buf("qh_c", (H, max(nc, 1), 128), bf)
+        ws.qh_n = _buf("qh_n", (H, max(L - nc, 1), 128), bf)  # (a rank of a sequence-parallel job may hold condition rows only)
+        ws.qm_c = _buf("qmax2_c", (H,), f32) if pl.use_bounds else None
+        ws.qm_n = _buf("qmax2_n", (H,), f32) if pl.use_bounds else None
+        if pl.exchange is not None:
             # dense blocks: K, V^T and the norm bounds of this rank's shard go straight into its slot of the exchange buffers
-            if not prescale or comm.world == 1:
-                mode = "gather"   # part launches are built for the pre-scaled-Q form
-            ex = self._exchange(tag, H, Sp, mode, int(self.exchange_chunks))
-        elif vc is not None:
+            ws.ex = self._exchange(pl.tag, H, Sp, pl.exchange, int(self.exchange_chunks))
+        elif pl.cached:
             # continuation: the working pair of ("use") has names of its own -- the uncached forward scans its zero-initialised K up to
             # the pad for the norm bound and must never find another forward's rows there; ("build") writes the cache's own tensors
-            if not build:
-                kh = _buf("kh_vc", (H, Sp, 128), bf, zero=True)
-                vt = _buf("vt_vc", (H, Sp // 64, 128, 64), bf, zero=True)
-                km = _buf("kmax2_vc", (H,), f32) if use_bounds else None
-                kcw = _buf("kcmp_vc", (H, Sp // blk, 128), bf) if use_bsa else None
-        else:
-            kh = _buf("kh", (H, Sp, 128), bf, zero=True)
-            vt = _buf("vt", (H, Sp // 64, 128, 64), bf)
-            km = _buf("kmax2", (H,), f32) if use_bounds else None
+            ws.kh = _buf("kh_vc", (H, Sp, 128), bf, zero=True)
+            ws.vt = _buf("vt_vc", (H, Sp // 64, 128, 64), bf, zero=True)
+            ws.km = _buf("kmax2_vc", (H,), f32) if pl.use_bounds else None
+            ws.kcw = _buf("kcmp_vc", (H, Sp // pl.blk, 128), bf) if pl.use_bsa else None
+        elif not pl.build:
+            ws.kh = _buf("kh", (H, Sp, 128), bf, zero=True)
+            ws.vt = _buf("vt", (H, Sp // 64, 128, 64), bf)
+            ws.km = _buf("kmax2", (H,), f32) if pl.use_bounds else None
             if comm is not None:  # block-sparse blocks gather K / V^T densely (the sparse kernel addresses [P][H][S][128])
-                kh_all = _buf("kh_all", (comm.world, H, Sp, 128), bf, zero=True)
-                vt_all = _buf("vt_all", (comm.world, H, Sp // 64, 128, 64), bf)
-        ao = _buf("ao", (L, C), bf)
-        ys = _buf("ys", (L, C), bf)
-        qc = _buf("qc", (L, C), bf)
-        kvt = _buf("kvt", (n_txt, 2 * C), bf)
-        kth = _buf("kth", (H, Ltp, 128), bf, zero=True)
-        vtt = _buf("vtt", (H, Ltp // 64, 128, 64), bf)
-        ffh = _buf("ffh", (L, 2 * Hd), bf)
-        ffg = _buf("ffg", (L, Hd), bf)
-        ald = ada.stride(0)
-        if use_bsa:
-            sparsity = self.bsa_params.get("sparsity")
-            cdf_thr = self.bsa_params.get("cdf_threshold")
-            if sparsity is None and cdf_thr is None:
-                raise ValueError("bsa_params needs sparsity and / or cdf_threshold (bsa_interface.py:265-274)")
+                ws.kh_all = _buf("kh_all", (comm.world, H, Sp, 128), bf, zero=True)
+                ws.vt_all = _buf("vt_all", (comm.world, H, Sp // 64, 128, 64), bf)
+        ws.ao = _buf("ao", (L, C), bf)
+        ws.ys = _buf("ys", (L, C), bf)
+        ws.qc = _buf("qc", (L, C), bf)
+        ws.kvt = _buf("kvt", (n_txt, 2 * C), bf)
+        ws.kth = _buf("kth", (H, Ltp, 128), bf, zero=True)
+        ws.vtt = _buf("vtt", (H, Ltp // 64, 128, 64), bf)
+        ws.ffh = _buf("ffh", (L, 2 * Hd), bf)
+        ws.ffg = _buf("ffg", (L, Hd), bf)
+        return ws
 
-            def select(scores):  # bsa_interface.py:265-274 -> (block indices, per-row counts or None)
-                if cdf_thr is None:
-                    return bsa.select_topk(scores, float(sparsity)), None
-                return bsa.select_cdf(scores, float(cdf_thr), None if sparsity is None else float(sparsity))
+    def _caption_kv(self, ws, emb, i, kth, vtt):
+        """Block i's caption keys / values (LCA:236-262) into kth [H, Ltp, 128] / vtt [H, Ltp / 64, 128, 64]."""
+        W, p = self._wl, f"blocks.{i}."
+        gemm(emb.y, W[p + "cross_attn.kv_linear.w"], W[p + "cross_attn.kv_linear.b"], ws.kvt, EPI_BF16)
+        self._heads(ws.kvt, 0, W[p + "cross_attn.k_norm"], None, None, kth, 0, emb.n_txt)
+        self._vt(ws.kvt, self.cfg.hidden_size, vtt, emb.n_txt)
 
-            fused_sel = not os.environ.get("WF_BSA_TORCH_SELECT")  # (the env switch keeps the torch selection paths testable)
-            self.last_bsa_indices = []
+    def _shared_caption_kv(self, pl, ws, emb):
+        """Sequence-parallel jobs: the caption K / V^T of layer i are computed by rank i (mod P) only and all-gathered once per forward
+        (see dit.py: work that does not shrink with the token shard).  -> None, or the gathered buffers with the events of their
+        gathers, which the first cross-attention waits for."""
+        cfg, comm = self.cfg, self.comm
+        if comm is None or comm.world <= 1:
+            return None
+        bf, H, Ltp = torch.bfloat16, cfg.num_heads, _pad64(emb.n_txt)
+        _buf = self._tagged_buf(pl)
+        P_, nl = comm.world, (cfg.depth + comm.world - 1) // comm.world
+        loc = [_buf("ckv_loc0", (nl, H, Ltp, 128), bf, zero=True), _buf("ckv_loc1", (nl, H, Ltp // 64, 128, 64), bf)]
+        allb = [_buf(f"ckv_all{j}", (P_,) + tuple(t.shape), bf) for j, t in enumerate(loc)]
+        for j in range(nl):
+            i = comm.rank + P_ * j
+            if i >= cfg.depth:
+                break
+            self._caption_kv(ws, emb, i, loc[0][j], loc[1][j])
+        return SimpleNamespace(allb=allb, P=P_, events=[comm.all_gather_async(a_, l_) for a_, l_ in zip(allb, loc)])
 
-        # sequence-parallel jobs: the caption K / V^T of layer i are computed by rank i (mod P) only and all-gathered once per forward (see
-        # dit.py: work that does not shrink with the token shard)
-        ctx_shared = ctx_events = None
-        if comm is not None and comm.world > 1:
-            P_, nl = comm.world, (cfg.depth + comm.world - 1) // comm.world
-            loc = [_buf("ckv_loc0", (nl, H, Ltp, 128), bf, zero=True), _buf("ckv_loc1", (nl, H, Ltp // 64, 128, 64), bf)]
-            allb = [_buf(f"ckv_all{j}", (P_,) + tuple(t.shape), bf) for j, t in enumerate(loc)]
-            for j in range(nl):
-                i = comm.rank + P_ * j
-                if i >= cfg.depth:
-                    break
-                p = f"blocks.{i}."
-                gemm(y, W[p + "cross_attn.kv_linear.w"], W[p + "cross_attn.kv_linear.b"], kvt, EPI_BF16)
-                self._heads(kvt, 0, W[p + "cross_attn.k_norm"], None, None, loc[0][j], 0, n_txt)
-                self._vt(kvt, C, loc[1][j], n_txt)
-            ctx_events = [comm.all_gather_async(a_, l_) for a_, l_ in zip(allb, loc)]
-            ctx_shared = (allb, P_)
+    # ---- self-attention, one method per path; each decides in ONE place whose K / V^T / bound it runs on ------------------------
+    def _sa_queries(self, pl, ws, i):
+        """Normalised, rotated (and in the dense paths pre-scaled) condition / noise queries of this rank's rows."""
+        qn = self._wl[f"blocks.{i}.attn.q_norm"]
+        self._heads(ws.qkv, 0, qn, pl.cos, pl.sin, ws.qh_c, 0, pl.nc, out_scale=pl.q_scale)
+        self._heads(ws.qkv, 0, qn, pl.cos, pl.sin, ws.qh_n, pl.nc, pl.L, out_scale=pl.q_scale)
 
-        for i in range(cfg.depth):
-            p = f"blocks.{i}."
-            m = ada[:, i * 6 * C:(i + 1) * 6 * C]
-            shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp = (m[:, j * C:(j + 1) * C] for j in range(6))
-            # ---- self-attention (LCD:91-104, LCA:105-145) ----
-            self._ln(x, scale_msa, shift_msa, ald, tpf, True, hbuf, row0=lo, gidx=gidx)
-            gemm(hbuf, W[p + "attn.qkv.w"], W[p + "attn.qkv.b"], qkv, EPI_BF16)
-            if use_bsa:
-                # LCA:57-66 + bsa_interface.py:612-659 on rows that already are in block order: gating = mean-pooled q / k blocks ->
-                # bf16 block scores -> top-k / cdf selection per query block -> sparse attention over the selected key blocks
-                self._heads(qkv, 0, W[p + "attn.q_norm"], cos, sin, qh_c, 0, nc)
-                self._heads(qkv, 0, W[p + "attn.q_norm"], cos, sin, qh_n, nc, L)
-                if vc is not None and not build:
-                    # the cached keys, values and pooled means in front (kc is whole blocks), this step's appended behind them
-                    kh[:, :kc].copy_(cache.k[i])
-                    vt[:, :kc // 64].copy_(cache.vt[i])
-                    kcw[:, :kc // blk].copy_(cache.kcmp[i])
-                    self._heads(qkv, C, W[p + "attn.k_norm"], cos, sin, kh[:, kc:], 0, L, lout=Sp)
-                    self._vt_at(qkv, 2 * C, vt, kc, L)
-                    call("wf_lc_mean_pool_blocks_at", kh[:, kc:].data_ptr(), Sp, kcw.data_ptr(), Sp // blk, kc // blk, H, L, blk,
-                         ops.stream())
-                    kcmp = kcw
-                else:
-                    if build:
-                        kh, vt = cache.k[i], cache.vt[i]
-                    self._heads(qkv, C, W[p + "attn.k_norm"], cos, sin, kh, 0, L)
-                    self._vt(qkv, 2 * C, vt, L)
-                    kcmp = bsa.mean_pool(kh, blk)  # this rank's key blocks (zero rows past the last token pool to zero blocks)
-                    if build:
-                        cache.kcmp[i].copy_(kcmp)
-                kk, vv = kh, vt
-                if comm is not None:
-                    evs = (comm.all_gather_async(kh_all, kh), comm.all_gather_async(vt_all, vt))
-                    kc_all = torch.empty((comm.world,) + tuple(kcmp.shape), dtype=bf, device=dev)
-                    comm.all_gather(kc_all, kcmp)
-                    kcmp = kc_all.permute(1, 0, 2, 3).reshape(H, -1, 128)
-                    for ev in evs:
-                        if ev is not None:
-                            torch.cuda.current_stream().wait_event(ev)
-                    kk, vv = kh_all, vt_all
-                kcmp = kcmp[:, :L_all // blk].contiguous()
-                picked = []
-                for nrows, qrows, orows, nkb in ((nc, qh_c, ao[:nc], nc_all // blk), (L - nc, qh_n, ao[nc:], L_all // blk)):
-                    if nrows == 0:
-                        continue
-                    sc = bsa.block_scores(bsa.mean_pool(qrows, blk), kcmp if nkb == L_all // blk else kcmp[:, :nkb].contiguous())
-                    if fused_sel and nkb <= bsa.TOPK_MAX_BLOCKS and cdf_thr is None:  # selection + list building in one kernel
-                        picked.append(bsa.sparse_attention_topk(qrows, kk, vv, orows, sc, float(sparsity), scale, blk))
-                    elif fused_sel and nkb <= bsa.TOPK_MAX_BLOCKS:  # the cdf rule: counts (sort + scan in LDS), then the same list kernel
-                        picked.append(bsa.sparse_attention_cdf(qrows, kk, vv, orows, sc, float(cdf_thr),
-                                                               None if sparsity is None else float(sparsity), scale, blk))
-                    else:
-                        idx, lens = select(sc)
-                        bsa.sparse_attention(qrows, kk, vv, orows, idx, scale, nkb, lens, blk)
-                        picked.append(idx if lens is None else (idx, lens))
-                self.last_bsa_indices.append(picked)
-                if build:
-                    cache.bsa_indices.append(picked[0])
-                    if i == cfg.depth - 1:
-                        return  # (the dense build returns in front of its last attention; this one keeps the last selection too)
-            else:
-                self._heads(qkv, 0, W[p + "attn.q_norm"], cos, sin, qh_c, 0, nc, out_scale=q_scale)
-                self._heads(qkv, 0, W[p + "attn.q_norm"], cos, sin, qh_n, nc, L, out_scale=q_scale)
-                if vc is not None and not build:
-                    # LCA:163-172 with the rotation already in the cache: cached keys [0, kc), this step's keys behind them
-                    ct = cache.vt.shape[2]
-                    kh[:, :kc].copy_(cache.k[i, :, :kc])
-                    vt[:, :ct].copy_(cache.vt[i])
-                    self._heads(qkv, C, W[p + "attn.k_norm"], cos, sin, kh[:, kc:], 0, L, lout=Sp)
-                    self._vt_at(qkv, 2 * C, vt, kc, L)
-                    if use_bounds:
-                        # the un-tracked softmax body is only safe under a bound over ALL kc + L keys: the cached rows' maximum, raised
-                        # by the new rows' (wf_head_max_norm2 only ever raises `out`; its row window is offset to key kc)
-                        km.copy_(cache.kmax2[i])
-                        call("wf_head_max_norm2", kh[:, kc:].data_ptr(), H, L, Sp, km.data_ptr(), ops.stream())
-                    self.last_kmax2, self.last_vc_keys = km, (kh, kc + L)
-                elif ex is None:
-                    if build:
-                        kh, vt, km = cache.k[i], cache.vt[i], cache.kmax2[i]
-                    self._heads(qkv, C, W[p + "attn.k_norm"], cos, sin, kh, 0, L)
-                    self._vt(qkv, 2 * C, vt, L)
-                    if use_bounds or build:  # zero rows past L do not raise a maximum: the whole (padded) shard is scanned
-                        head_max_norm2(kh, Sp, km)
-                    if build and i == cfg.depth - 1:
-                        return  # the last block's keys are in the cache: nothing reads the condition stream behind them
-                else:
-                    for g in range(ex.G):
-                        r0, r1 = ex.chunk_rows(g, L)
-                        if r1 > r0:
-                            self._heads(qkv, C, W[p + "attn.k_norm"], cos, sin, ex.own_k(g), r0, r1)
-                            self._vt(qkv[r0:r1], 2 * C, ex.own_vt(g), r1 - r0)
-                            if use_bounds:
-                                head_max_norm2(ex.own_k(g), ex.chunk_len(g), ex.own_km(g))
-                    ex.launch()
-                    yield i
-                if use_bounds and nc > 0:
-                    head_max_norm2(qh_c, nc, qm_c)
-                if use_bounds and L - nc > 0:
-                    head_max_norm2(qh_n, L - nc, qm_n)
-                if ex is None:
-                    if nc > 0:  # condition tokens see condition tokens only (LCA:127-131)
-                        attention(qh_c, kh, vt, ao[:nc], nc_all, sa_scale, kmax2=km, qmax2=qm_c)
-                    if L - nc > 0:  # noise tokens see everything (LCA:133-134)
-                        attention(qh_n, kh, vt, ao[nc:], L_all, sa_scale, profile=True, kmax2=km, qmax2=qm_n)
-                else:
-                    # the noise queries first: their sweep is what the exchange hides under; the condition queries see the first nc_all
-                    # keys only (rank 0's first rows), their windows are ready by then
-                    if L - nc > 0:
-                        attention_exchange(qh_n, ex, ao[nc:], L_all, sa_scale, qm_n, use_bounds=use_bounds, profile=True, release=False)
-                    if nc > 0:
-                        attention_exchange(qh_c, ex, ao[:nc], nc_all, sa_scale, qm_c, use_bounds=use_bounds, release=False,
-                                           comm_profile=L - nc <= 0)
-                    ex.wait_all()
-            gemm(ao, W[p + "attn.proj.w"], W[p + "attn.proj.b"], ys, EPI_BF16)
-            self._resid(x, ys, gate_msa, ald, tpf, row0=lo, gidx=gidx)
-            # ---- cross-attention on the noise tokens (LCD:108-111, LCA:218-276) ----
-            if L - nc > 0:
-                self._ln(x[nc:], W[p + "norm.w"], W[p + "norm.b"], 0, 0, False, hbuf[nc:])
-                gemm(hbuf[nc:], W[p + "cross_attn.q_linear.w"], W[p + "cross_attn.q_linear.b"], qc[nc:], EPI_BF16)
-                self._heads(qc, 0, W[p + "cross_attn.q_norm"], None, None, qh_n, nc, L)
-                if ctx_shared is not None:
-                    if ctx_events is not None:
-                        for ev in ctx_events:
-                            if ev is not None:
-                                torch.cuda.current_stream().wait_event(ev)
-                        ctx_events = None
-                    kth_i, vtt_i = (a_[i % ctx_shared[1], i // ctx_shared[1]] for a_ in ctx_shared[0])
-                else:
-                    gemm(y, W[p + "cross_attn.kv_linear.w"], W[p + "cross_attn.kv_linear.b"], kvt, EPI_BF16)
-                    self._heads(kvt, 0, W[p + "cross_attn.k_norm"], None, None, kth, 0, n_txt)
-                    self._vt(kvt, C, vtt, n_txt)
-                    kth_i, vtt_i = kth, vtt
-                attention(qh_n, kth_i, vtt_i, ao[nc:], n_txt, scale)
-                gemm(ao[nc:], W[p + "cross_attn.proj.w"], W[p + "cross_attn.proj.b"], ys[nc:], EPI_BF16)
-                self._resid(x[nc:], ys[nc:], None, 0, 0)
-            # ---- SwiGLU FFN (LCD:113-120, LCB:36-37) ----
-            self._ln(x, scale_mlp, shift_mlp, ald, tpf, True, hbuf, row0=lo, gidx=gidx)
-            gemm(hbuf, W[p + "ffn.w13"], None, ffh, EPI_BF16)
-            call("wf_lc_swiglu", ffh.data_ptr(), ffh.stride(0), ffg.data_ptr(), L, Hd, ops.stream())
-            gemm(ffg, W[p + "ffn.w2"], None, ys, EPI_BF16)
-            self._resid(x, ys, gate_mlp, ald, tpf, row0=lo, gidx=gidx)
+    def _sa_query_bounds(self, pl, ws):
+        if pl.use_bounds and pl.nc > 0:
+            head_max_norm2(ws.qh_c, pl.nc, ws.qm_c)
+        if pl.use_bounds and pl.L - pl.nc > 0:
+            head_max_norm2(ws.qh_n, pl.L - pl.nc, ws.qm_n)
 
-        # ---- final layer (LCB:159-168) + unpatchify (LCD:371-392) ----
-        assert not build
-        self._ln(x, fmod[:, C:], fmod[:, :C], fmod.stride(0), tpf, True, hbuf, row0=lo, gidx=gidx)
-        yo = _buf("yo", (L, 4 * cfg.out_channels), f32)
-        gemm(hbuf, W["final_layer.linear.w"], W["final_layer.linear.b"], yo, EPI_F32)
-        if comm is not None:
-            yo = gather_rows(comm, yo, plan).contiguous()
-        if use_bsa:  # velocity rows back to (T, H, W) order: bsa_interface.py:606-610 (fp32 rows moved as 16-byte chunks)
-            yt = torch.empty_like(yo)
-            call("wf_gather_rows_bf16", yo.data_ptr(), 2 * yo.stride(0), pos.data_ptr(), yt.data_ptr(), 2 * yt.stride(0), L_all - kc,
+    def _sa_keys(self, pl, ws, i, kh, vt, km):
+        """This forward's L rows as the WHOLE key set: K into kh, V^T into vt, the norm bound into km (None: not wanted)."""
+        self._heads(ws.qkv, self.cfg.hidden_size, self._wl[f"blocks.{i}.attn.k_norm"], pl.cos, pl.sin, kh, 0, pl.L)
+        self._vt(ws.qkv, 2 * self.cfg.hidden_size, vt, pl.L)
+        if km is not None:  # zero rows past L do not raise a maximum: the whole (padded) shard is scanned
+            head_max_norm2(kh, pl.Sp, km)
+
+    def _sa_attend(self, pl, ws, kh, vt, km):
+        self._sa_query_bounds(pl, ws)
+        if pl.nc > 0:  # condition tokens see condition tokens only (LCA:127-131)
+            attention(ws.qh_c, kh, vt, ws.ao[:pl.nc], pl.nc_all, pl.sa_scale, kmax2=km, qmax2=ws.qm_c)
+        if pl.L - pl.nc > 0:  # noise tokens see everything (LCA:133-134)
+            attention(ws.qh_n, kh, vt, ws.ao[pl.nc:], pl.L_all, pl.sa_scale, profile=True, kmax2=km, qmax2=ws.qm_n)
+
+    def _sa_dense_local(self, pl, ws, i):
+        """One GPU, no cache: keys in this forward's own workspaces."""
+        self._sa_queries(pl, ws, i)
+        self._sa_keys(pl, ws, i, ws.kh, ws.vt, ws.km)
+        self._sa_attend(pl, ws, ws.kh, ws.vt, ws.km)
+
+    def _sa_dense_exchange(self, pl, ws, i):
+        """Sequence parallel: K, V^T and the bounds of this rank's rows are written into its slots of the exchange buffers; yields
+        once, right after the exchange has been launched."""
+        ex, C, L, nc = ws.ex, self.cfg.hidden_size, pl.L, pl.nc
+        kn = self._wl[f"blocks.{i}.attn.k_norm"]
+        self._sa_queries(pl, ws, i)
+        for g in range(ex.G):
+            r0, r1 = ex.chunk_rows(g, L)
+            if r1 > r0:
+                self._heads(ws.qkv, C, kn, pl.cos, pl.sin, ex.own_k(g), r0, r1)
+                self._vt(ws.qkv[r0:r1], 2 * C, ex.own_vt(g), r1 - r0)
+                if pl.use_bounds:
+                    head_max_norm2(ex.own_k(g), ex.chunk_len(g), ex.own_km(g))
+        ex.launch()
+        yield i
+        self._sa_query_bounds(pl, ws)
+        # the noise queries first: their sweep is what the exchange hides under; the condition queries see the first nc_all
+        # keys only (rank 0's first rows), their windows are ready by then
+        if L - nc > 0:
+            attention_exchange(ws.qh_n, ex, ws.ao[nc:], pl.L_all, pl.sa_scale, ws.qm_n, use_bounds=pl.use_bounds, profile=True, release=False)
+        if nc > 0:
+            attention_exchange(ws.qh_c, ex, ws.ao[:nc], pl.nc_all, pl.sa_scale, ws.qm_c, use_bounds=pl.use_bounds, release=False,
+                               comm_profile=L - nc <= 0)
+        ex.wait_all()
+
+    def _sa_dense_cached(self, pl, ws, i, attend):
+        """Video continuation.  A build writes block i's rows of the cache in place (and always its norm bound); a step runs on the
+        "_vc" working pair: the cached keys in front, its own behind them."""
+        cache, C, H, L, kc, Sp = pl.cache, self.cfg.hidden_size, self.cfg.num_heads, pl.L, pl.kc, pl.Sp
+        self._sa_queries(pl, ws, i)
+        if pl.build:
+            kh, vt, km = cache.k[i], cache.vt[i], cache.kmax2[i]
+            self._sa_keys(pl, ws, i, kh, vt, km)
+        else:
+            kh, vt, km = ws.kh, ws.vt, ws.km
+            # LCA:163-172 with the rotation already in the cache: cached keys [0, kc), this step's keys behind them
+            ct = cache.vt.shape[2]
+            kh[:, :kc].copy_(cache.k[i, :, :kc])
+            vt[:, :ct].copy_(cache.vt[i])
+            self._heads(ws.qkv, C, self._wl[f"blocks.{i}.attn.k_norm"], pl.cos, pl.sin, kh[:, kc:], 0, L, lout=Sp)
+            self._vt_at(ws.qkv, 2 * C, vt, kc, L)
+            if pl.use_bounds:
+                # the un-tracked softmax body is only safe under a bound over ALL kc + L keys: the cached rows' maximum, raised
+                # by the new rows' (wf_head_max_norm2 only ever raises `out`; its row window is offset to key kc)
+                km.copy_(cache.kmax2[i])
+                call("wf_head_max_norm2", kh[:, kc:].data_ptr(), H, L, Sp, km.data_ptr(), ops.stream())
+            self.last_kmax2, self.last_vc_keys = km, (kh, kc + L)
+        if attend:
+            self._sa_attend(pl, ws, kh, vt, km)
+
+    def _sa_block_sparse(self, pl, ws, i):
+        """LCA:57-66 + bsa_interface.py:612-659 on rows that already are in block order: gating = mean-pooled q / k blocks ->
+        bf16 block scores -> top-k / cdf selection per query block -> sparse attention over the selected key blocks."""
+        from . import bsa
+        comm, cache, C, H, L, nc, kc, Sp, blk = self.comm, pl.cache, self.cfg.hidden_size, self.cfg.num_heads, pl.L, pl.nc, pl.kc, pl.Sp, pl.blk
+        kn = self._wl[f"blocks.{i}.attn.k_norm"]
+        self._sa_queries(pl, ws, i)  # (q_scale is 1: this Q also feeds the gating)
+        # the operands: kh / vt / kcmp_own = this rank's keys, values and pooled key blocks
+        if pl.cached:
+            # a step on a cache: the "_vc" working set, the cached keys, values and pooled means in front (kc is whole blocks), this
+            # step's appended behind them
+            kh, vt, kcmp_own = ws.kh, ws.vt, ws.kcw
+            kh[:, :kc].copy_(cache.k[i])
+            vt[:, :kc // 64].copy_(cache.vt[i])
+            kcmp_own[:, :kc // blk].copy_(cache.kcmp[i])
+            self._heads(ws.qkv, C, kn, pl.cos, pl.sin, kh[:, kc:], 0, L, lout=Sp)
+            self._vt_at(ws.qkv, 2 * C, vt, kc, L)
+            call("wf_lc_mean_pool_blocks_at", kh[:, kc:].data_ptr(), Sp, kcmp_own.data_ptr(), Sp // blk, kc // blk, H, L, blk, ops.stream())
+        else:
+            # a build writes block i's rows of the cache in place and copies the means there; else this forward's own workspaces
+            kh, vt = (cache.k[i], cache.vt[i]) if pl.build else (ws.kh, ws.vt)
+            self._sa_keys(pl, ws, i, kh, vt, None)
+            kcmp_own = bsa.mean_pool(kh, blk)  # this rank's key blocks (zero rows past the last token pool to zero blocks)
+            if pl.build:
+                cache.kcmp[i].copy_(kcmp_own)
+        kk, vv, kcmp_all = kh, vt, kcmp_own
+        if comm is not None:  # sequence parallel: every rank's shards, gathered (kh_all / vt_all are workspaces of their own)
+            evs = (comm.all_gather_async(ws.kh_all, kh), comm.all_gather_async(ws.vt_all, vt))
+            kc_all = torch.empty((comm.world,) + tuple(kcmp_own.shape), dtype=torch.bfloat16, device=self.device)
+            comm.all_gather(kc_all, kcmp_own)
+            kk, vv, kcmp_all = ws.kh_all, ws.vt_all, kc_all.permute(1, 0, 2, 3).reshape(H, -1, 128)
+            wait_events(evs)
+        kcmp = kcmp_all[:, :pl.L_all // blk].contiguous()
+        picked = []
+        for nrows, qrows, orows, nkb in ((nc, ws.qh_c, ws.ao[:nc], pl.nc_all // blk), (L - nc, ws.qh_n, ws.ao[nc:], pl.L_all // blk)):
+            if nrows == 0:
+                continue
+            sc = bsa.block_scores(bsa.mean_pool(qrows, blk), kcmp if nkb == pl.L_all // blk else kcmp[:, :nkb].contiguous())
+            picked.append(self._bsa_select_attend(pl, qrows, kk, vv, orows, sc, nkb))
+        self.last_bsa_indices.append(picked)
+        if pl.build:
+            cache.bsa_indices.append(picked[0])
+
+    def _bsa_select_attend(self, pl, qrows, kk, vv, orows, sc, nkb):
+        """Selection (bsa_interface.py:265-274) and sparse attention of one kind of query rows -> what last_bsa_indices keeps."""
+        from . import bsa
+        sparsity, cdf_thr, scale, blk = pl.sparsity, pl.cdf_thr, pl.scale, pl.blk
+        if pl.fused_sel and nkb <= bsa.TOPK_MAX_BLOCKS and cdf_thr is None:  # selection + list building in one kernel
+            return bsa.sparse_attention_topk(qrows, kk, vv, orows, sc, float(sparsity), scale, blk)
+        if pl.fused_sel and nkb <= bsa.TOPK_MAX_BLOCKS:  # the cdf rule: counts (sort + scan in LDS), then the same list kernel
+            return bsa.sparse_attention_cdf(qrows, kk, vv, orows, sc, float(cdf_thr), None if sparsity is None else float(sparsity), scale, blk)
+        if cdf_thr is None:  # -> (block indices, per-row counts or None)
+            idx, lens = bsa.select_topk(sc, float(sparsity)), None
+        else:
+            idx, lens = bsa.select_cdf(sc, float(cdf_thr), None if sparsity is None else float(sparsity))
+        bsa.sparse_attention(qrows, kk, vv, orows, idx, scale, nkb, lens, blk)
+        return idx if lens is None else (idx, lens)
+
+    def _cross_attention(self, pl, ws, emb, ctx, i):
+        """Cross-attention on the noise tokens (LCD:108-111, LCA:218-276); ctx: the gathered caption K / V^T of _shared_caption_kv."""
+        W, p, x, nc, L = self._wl, f"blocks.{i}.", emb.x, pl.nc, pl.L
+        self._ln(x[nc:], W[p + "norm.w"], W[p + "norm.b"], 0, 0, False, ws.hbuf[nc:])
+        gemm(ws.hbuf[nc:], W[p + "cross_attn.q_linear.w"], W[p + "cross_attn.q_linear.b"], ws.qc[nc:], EPI_BF16)
+        self._heads(ws.qc, 0, W[p + "cross_attn.q_norm"], None, None, ws.qh_n, nc, L)
+        if ctx is not None:
+            if ctx.events is not None:
+                wait_events(ctx.events)
+                ctx.events = None
+            kth_i, vtt_i = (a_[i % ctx.P, i // ctx.P] for a_ in ctx.allb)
+        else:
+            self._caption_kv(ws, emb, i, ws.kth, ws.vtt)
+            kth_i, vtt_i = ws.kth, ws.vtt
+        attention(ws.qh_n, kth_i, vtt_i, ws.ao[nc:], emb.n_txt, pl.scale)
+        gemm(ws.ao[nc:], W[p + "cross_attn.proj.w"], W[p + "cross_attn.proj.b"], ws.ys[nc:], EPI_BF16)
+        self._resid(x[nc:], ws.ys[nc:], None, 0, 0)
+
+    def _final_layer(self, pl, ws, emb):
+        """Final layer (LCB:159-168) + unpatchify (LCD:371-392) -> velocity [out_channels, T, Hh, Ww] fp32."""
+        from .parallel import gather_rows
+        cfg, W, fmod, C = self.cfg, self._wl, emb.fmod, self.cfg.hidden_size
+        self._ln(emb.x, fmod[:, C:], fmod[:, :C], fmod.stride(0), pl.tpf, True, ws.hbuf, row0=pl.lo, gidx=pl.gidx)
+        yo_own = self._tagged_buf(pl)("yo", (pl.L, 4 * cfg.out_channels), torch.float32)
+        gemm(ws.hbuf, W["final_layer.linear.w"], W["final_layer.linear.b"], yo_own, EPI_F32)
+        yo = yo_own if self.comm is None else gather_rows(self.comm, yo_own, pl.shard).contiguous()
+        yt = torch.empty_like(yo) if pl.use_bsa else yo
+        if pl.use_bsa:  # velocity rows back to (T, H, W) order: bsa_interface.py:606-610 (fp32 rows moved as 16-byte chunks)
+            call("wf_gather_rows_bf16", yo.data_ptr(), 2 * yo.stride(0), pl.pos.data_ptr(), yt.data_ptr(), 2 * yt.stride(0), pl.L_tok,
                  2 * yo.shape[1], ops.stream())
-            yo = yt
-        out = torch.empty((cfg.out_channels, T, Hh, Ww), dtype=f32, device=dev)
-        call("wf_unpatchify", yo.data_ptr(), out.data_ptr(), cfg.out_channels, T, Hh, Ww, ops.stream())
-        result[0] = out
+        out = torch.empty((cfg.out_channels, pl.T, pl.Hh, pl.Ww), dtype=torch.float32, device=self.device)
+        call("wf_unpatchify", yt.data_ptr(), out.data_ptr(), cfg.out_channels, pl.T, pl.Hh, pl.Ww, ops.stream())
+        return out
 
     def _batch_samples(self, hidden_states, timestep, encoder_hidden_states, encoder_attention_mask):
         """The diffusers-style batch -> one (x_in, timesteps, caption, caption_mask) of forward_tokens per sample."""
@@ -1051,16 +1122,30 @@ class LongCatVideoTransformer3DModel:
             raise NotImplementedError("the dense condition cache does not serve block-sparse attention: disable_bsa() first, or use "
                                       "cache_condition_blocks() / forward_cached_blocks()")
 
+    def _cond_input(self, cond_latents):
+        """cond_latents [16, ncl, Hh, Ww] -> (the same bf16, contiguous, on the device; ncl, Hh, Ww, condition tokens)."""
+        x = cond_latents if cond_latents.dtype == torch.bfloat16 else ops.cast(cond_latents.contiguous(), torch.bfloat16)
+        x = x.to(self.device).contiguous()
+        _, ncl, Hh, Ww = x.shape
+        return x, ncl, Hh, Ww, ncl * (Hh // 2) * (Ww // 2)
+
+    def _check_cache_origin(self, cache: _CondCache, latent_hw, builder: str):
+        """Either kind of cache is bound to the weights it was built with and to its latent size; builder: who makes a new one."""
+        if cache.owner is not self._token or cache.wver != self._wver or cache.loras != tuple(self.active_loras) \
+                or cache.linear_precision != self.linear_precision:
+            raise ValueError("the condition cache was built with other weights (another model, a weight load / weights_changed(), a LoRA "
+                             f"switch or another linear_precision since): build it again with {builder}")
+        if tuple(latent_hw) != tuple(cache.latent_hw):
+            raise ValueError(f"the condition cache holds {cache.latent_hw[0]} x {cache.latent_hw[1]} latent frames, the input is "
+                             f"{latent_hw[0]} x {latent_hw[1]}")
+
     def cache_condition(self, cond_latents: torch.Tensor) -> LongCatCondCache:
         """PIPE:336-348 (`_cache_clean_latents`: timestep 0, skip_crs_attn, return_kv).  cond_latents [16, ncl, Hh, Ww] (normalised
         condition latents, bf16 or cast to it) -> the cache of their keys / values in every block.  Stays on the GPU
         (`offload_kv_cache` has no counterpart); shared by the samples of a CFG batch (LCA:163-165)."""
         self._vc_guard()
         cfg, dev = self.cfg, self.device
-        x = cond_latents if cond_latents.dtype == torch.bfloat16 else ops.cast(cond_latents.contiguous(), torch.bfloat16)
-        x = x.to(dev).contiguous()
-        _, ncl, Hh, Ww = x.shape
-        nc = ncl * (Hh // 2) * (Ww // 2)
+        x, ncl, Hh, Ww, nc = self._cond_input(cond_latents)
         assert nc > 0
         H, ncp = cfg.num_heads, _pad64(nc)
         cache = LongCatCondCache(
@@ -1069,21 +1154,14 @@ class LongCatVideoTransformer3DModel:
             kmax2=torch.zeros((cfg.depth, H), dtype=torch.float32, device=dev),
             ncl=ncl, nc=nc, latent_hw=(Hh, Ww), owner=self._token, wver=self._wver, loras=tuple(self.active_loras),
             linear_precision=self.linear_precision)
-        for _ in self._forward_steps(x, [0.0] * ncl, None, None, ncl, "", [None], "gather", vc=("build", cache)):
-            pass
+        run(self._forward_steps(x, [0.0] * ncl, None, None, ncl, "", [None], "gather", vc=("build", cache)))
         return cache
 
     def _check_cache(self, cache: LongCatCondCache, latent_hw):
         self._vc_guard()
         if not isinstance(cache, LongCatCondCache):
             raise ValueError("forward_cached / forward_tokens_cached take the dense LongCatCondCache of cache_condition()")
-        if cache.owner is not self._token or cache.wver != self._wver or cache.loras != tuple(self.active_loras) \
-                or cache.linear_precision != self.linear_precision:
-            raise ValueError("the condition cache was built with other weights (another model, a weight load / weights_changed(), a LoRA "
-                             "switch or another linear_precision since): build it again with cache_condition()")
-        if tuple(latent_hw) != tuple(cache.latent_hw):
-            raise ValueError(f"the condition cache holds {cache.latent_hw[0]} x {cache.latent_hw[1]} latent frames, the input is "
-                             f"{latent_hw[0]} x {latent_hw[1]}")
+        self._check_cache_origin(cache, latent_hw, "cache_condition()")
 
     def forward_tokens_cached(self, x_in: torch.Tensor, timesteps, caption: torch.Tensor, caption_mask: Optional[torch.Tensor],
                               cache: LongCatCondCache) -> torch.Tensor:
@@ -1093,8 +1171,7 @@ class LongCatVideoTransformer3DModel:
         on the noise tokens, the caption or the step."""
         self._check_cache(cache, x_in.shape[-2:])
         out = [None]
-        for _ in self._forward_steps(x_in, timesteps, caption, caption_mask, 0, "", out, "gather", vc=("use", cache)):
-            pass
+        run(self._forward_steps(x_in, timesteps, caption, caption_mask, 0, "", out, "gather", vc=("use", cache)))
         return out[0]
 
     def forward_cached(self, hidden_states: torch.Tensor, timestep: torch.Tensor, encoder_hidden_states: torch.Tensor,
@@ -1131,14 +1208,11 @@ class LongCatVideoTransformer3DModel:
         once, in block order, and K / V^T / the pooled block means of every DiT block stay resident."""
         cq = self._vc_blocks_guard()
         cfg, dev = self.cfg, self.device
-        x = cond_latents if cond_latents.dtype == torch.bfloat16 else ops.cast(cond_latents.contiguous(), torch.bfloat16)
-        x = x.to(dev).contiguous()
-        _, ncl, Hh, Ww = x.shape
+        x, ncl, Hh, Ww, nc = self._cond_input(cond_latents)
         if ncl < 2 or ncl % cq[0]:
             raise ValueError(f"the block-ordered condition cache needs at least 2 condition latent frames in whole {cq[0]}-frame blocks, "
                              f"not {ncl} (the reference pads them: pipeline_longcat_video.py:1417-1419)")
         blk = cq[0] * cq[1] * cq[2]
-        nc = ncl * (Hh // 2) * (Ww // 2)
         sp, cdf = self._vc_blocks_selection(nc // blk)
         H, bf = cfg.num_heads, torch.bfloat16
         cache = LongCatBlockCondCache(
@@ -1147,21 +1221,14 @@ class LongCatVideoTransformer3DModel:
             kcmp=torch.empty((cfg.depth, H, nc // blk, 128), dtype=bf, device=dev), bsa_indices=[],
             ncl=ncl, nc=nc, latent_hw=(Hh, Ww), chunk=cq, sparsity=sp, cdf_threshold=cdf, owner=self._token, wver=self._wver,
             loras=tuple(self.active_loras), linear_precision=self.linear_precision)
-        for _ in self._forward_steps(x, [0.0] * ncl, None, None, ncl, "", [None], "gather", vc=("build", cache)):
-            pass
+        run(self._forward_steps(x, [0.0] * ncl, None, None, ncl, "", [None], "gather", vc=("build", cache)))
         return cache
 
     def _check_block_cache(self, cache: LongCatBlockCondCache, latent_hw, T: int):
         cq = self._vc_blocks_guard()
         if not isinstance(cache, LongCatBlockCondCache):
             raise ValueError("forward_cached_blocks / forward_tokens_cached_blocks take the LongCatBlockCondCache of cache_condition_blocks()")
-        if cache.owner is not self._token or cache.wver != self._wver or cache.loras != tuple(self.active_loras) \
-                or cache.linear_precision != self.linear_precision:
-            raise ValueError("the condition cache was built with other weights (another model, a weight load / weights_changed(), a LoRA "
-                             "switch or another linear_precision since): build it again with cache_condition_blocks()")
-        if tuple(latent_hw) != tuple(cache.latent_hw):
-            raise ValueError(f"the condition cache holds {cache.latent_hw[0]} x {cache.latent_hw[1]} latent frames, the input is "
-                             f"{latent_hw[0]} x {latent_hw[1]}")
+        self._check_cache_origin(cache, latent_hw, "cache_condition_blocks()")
         blk = cq[0] * cq[1] * cq[2]
         tpf = (latent_hw[0] // 2) * (latent_hw[1] // 2)
         if cache.chunk != cq or (cache.sparsity, cache.cdf_threshold) != self._vc_blocks_selection((cache.nc + T * tpf) // blk):
@@ -1176,8 +1243,7 @@ class LongCatVideoTransformer3DModel:
         the noise-query selection over all (cache.nc + L) / block key blocks."""
         self._check_block_cache(cache, x_in.shape[-2:], x_in.shape[1])
         out = [None]
-        for _ in self._forward_steps(x_in, timesteps, caption, caption_mask, 0, "", out, "gather", vc=("use", cache)):
-            pass
+        run(self._forward_steps(x_in, timesteps, caption, caption_mask, 0, "", out, "gather", vc=("use", cache)))
         return out[0]
 
     def forward_cached_blocks(self, hidden_states: torch.Tensor, timestep: torch.Tensor, encoder_hidden_states: torch.Tensor,
