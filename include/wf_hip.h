@@ -374,6 +374,33 @@ int wf_gather_rows_bf16(const void* in, int64_t ld_in, const int* index, void* o
 int wf_attn_bsa_fwd(const void* Q, const void* K, const void* Vt, void* O, int H, int Lq, int Lkp, int seg_len, int ldo,
                     float softmax_scale, const int* group_lists, const int* group_counts, int max_entries, int block, void* stream);
 
+/* ---- UMT5 text encoder (csrc/t5.hip; HF = transformers/models/umt5/modeling_umt5.py, the class RUN:203-204 / PIPE:21 load as
+ *      UMT5EncoderModel; worldforge_amd/umt5.py is the host).  The encoder's linears are wf_gemm_bf16; its residual stream is fp32. ---- */
+/* UMT5Attention.forward of an encoder layer (HF: scores = q k^T with NO 1/sqrt(d) factor, + position_bias (compute_bias: the layer's own
+ * relative_attention_bias embedding at _relative_position_bucket(key - query)) + the extended attention mask, softmax in fp32, P . V):
+ *   s[h][i][j] = q_i . k_j + bias[h * num_buckets + bucket_lut[j - i + (lmax - 1)]],  j < kv_len;  O = softmax_j(s) V.
+ * Q, K, V bf16 [L, ldqkv] with head h at columns h*64 (three column slices of one stacked QKV GEMM output; ldqkv % 8 == 0, 16-byte
+ * aligned), O bf16 [L, ldo] (ldo % 4 == 0, 8-byte aligned), bias f32 [H][num_buckets], bucket_lut uint8 [2 * lmax - 1] (built once by the
+ * host from the bidirectional bucket rule; a byte >= num_buckets is read as num_buckets - 1).  Keys j >= kv_len do not exist (HF adds
+ * finfo.min to their scores: the same for kv_len >= 1) and their K / V rows are never read; ALL L query rows are computed, the pad rows
+ * included, as HF returns them.  Softmax in fp32 with the exact row maximum, P rounded once to bf16, both products on bf16 MFMA with fp32
+ * accumulation, the row sum of the un-rounded p in fp32, one rounding of the output.  WF_EINVAL before any device work unless
+ * 1 <= kv_len <= L <= min(512, lmax), H >= 1, 1 <= num_buckets <= 256. */
+int wf_t5_attn_fwd(const void* Q, const void* K, const void* V, int ldqkv, void* O, int ldo, const float* bias, const void* bucket_lut,
+                   int lmax, int num_buckets, int H, int L, int kv_len, void* stream);
+/* UMT5DenseGatedActDense's gate (HF: hidden_gelu = gelu_new(wi_0(x)); hidden_linear = wi_1(x); hidden_gelu * hidden_linear): in f32
+ * [M, ld] with wi_0 x in columns [0, F) and wi_1 x in [F, 2F) -- ONE wf_gemm_bf16 over the stacked [wi_0; wi_1] weight with WF_EPI_F32 --
+ * -> out bf16 [M, F] = rn_bf16(0.5 g (1 + tanh(sqrt(2/pi) (g + 0.044715 g^3))) * u), rounded once; finite for every finite g, u whose
+ * product is (|g| up to 1e4 and beyond: tanh saturates).  F % 4 == 0, ld % 4 == 0. */
+int wf_t5_gated_gelu(const float* in, int64_t ld, void* out, int M, int F, void* stream);
+/* UMT5LayerNorm (HF: variance = x.float().pow(2).mean(-1); x * rsqrt(variance + eps) * weight; no mean subtraction, no bias): x f32
+ * [L, C] -> out bf16 [L, C], one rounding; the sum of squares in fp32 in a fixed order.  weight f32 [C]; C % 4 == 0.  (wf_rms_silu_cl
+ * is F.normalize with a clamp on the norm, wf_rmsnorm_heads reads bf16 and writes head-major: neither has this contract.) */
+int wf_t5_rmsnorm(const float* x, const float* weight, void* out, int L, int C, float eps, void* stream);
+/* shared / encoder.embed_tokens (HF: inputs_embeds = self.embed_tokens(input_ids)): ids int32 [L], table bf16 [V, C] -> out f32 [L, C],
+ * exact.  The host refuses ids outside [0, V) (ValueError) before the call; the kernel clamps and never reads outside the table. */
+int wf_t5_embed(const int* ids, const void* table, float* out, int L, int V, int C, void* stream);
+
 /* ---- 3D causal VAE (wan/modules/vae.py; the in-tree statement of diffusers' AutoencoderKLWan), channels-last ----------- */
 /* CausalConv3d / Conv2d as implicit GEMM on MFMA (vae.py:17-36, 76-96, 186-220).  in bf16 [Ti,Hi,Wi,Cin] (Cin % 32 == 0),
  * w bf16 [Cout][kt*kh*kw][Cin], bias f32; out (f32 and/or bf16) [To,Ho,Wo,Cout] (+ resid f32 of the same shape).

@@ -36,6 +36,7 @@ SOURCES = {
     "attention.hip": [],
     "dit_ops.hip": [],
     "longcat_ops.hip": ["-ffp-contract=off"],
+    "t5.hip": [],
     "vae_ops.hip": [],
     "conv.hip": [],
     "warp.hip": ["-ffp-contract=off"],

@@ -30,8 +30,11 @@ Same argument names, defaults and meaning as RUN:503-556.  Stated deviations:
     offload_kv_cache are not built, so the reference's default continuation tail is absent.
   * prompt_clean (PIPE:101) uses ftfy when it is importable, else only the HTML-unescape and white-space steps.
 Load time and peak host memory on a real checkpoint are NOT MEASURED: no real checkpoint has been available to this project.  For the
-same reason the route through the folder's own tokenizer / text_encoder (encode_with_transformers) has never been run; it encodes
-BEFORE the DiT and the VAE are loaded, so that UMT5 and the models are never resident together.
+same reason the default route through the folder's own tokenizer / text_encoder with the Hugging Face model class
+(--text-encoder transformers, encode_with_transformers) has never been run.  --text-encoder native (encode_native) runs the folder's
+UMT5 weights on this engine's own kernels instead (worldforge_amd/umt5.py; pinned against the Hugging Face module at test size by
+tests/test_gpu_umt5.py); only the tokenizer, data plus a host library, still comes from `transformers`.  Either route encodes BEFORE
+the DiT and the VAE are loaded, so that UMT5 and the models are never resident together.
 """
 from __future__ import annotations
 
@@ -121,6 +124,18 @@ def encode_with_transformers(checkpoint_dir: str, prompt: str, negative_prompt: 
     return out
 
 
+def encode_native(checkpoint_dir: str, prompt: str, negative_prompt: Optional[str], device, max_sequence_length: int = 512, tokenizer=None):
+    """encode_with_transformers with the encoder of worldforge_amd/umt5.py in place of the Hugging Face model class: the same keys,
+    shapes and dtypes ([1, 1, 512, C] bf16 embeddings, all rows, plus the tokenizer's mask), every tensor operation in libwf_hip.so.
+    tokenizer: a callable with the Hugging Face tokenizer signature to use instead of the folder's `tokenizer/` (tests)."""
+    from . import umt5
+    texts = {k: _prompt_clean(v) for k, v in (("prompt", prompt), ("negative_prompt", negative_prompt)) if v is not None}
+    out = {}
+    for key, (h, mask) in umt5.encode_prompts(checkpoint_dir, texts, device, tokenizer=tokenizer, max_sequence_length=max_sequence_length).items():
+        out[key + "_embeds"], out[key + "_attention_mask"] = umt5.to_longcat(h, mask)
+    return out
+
+
 def pick_size(image_height: int, image_width: int, resolution: str = "480p", height: Optional[int] = None, width: Optional[int] = None):
     """(height, width) of stage 1: --height x --width if given, else harness.target_size on the image's aspect ratio with the pixel
     budget of --resolution (480 * 832 or 720 * 1280).  A 16:9 image gives 464 x 832 at 480p (the reference's bucket table: 480 x 832)
@@ -147,7 +162,7 @@ def run(checkpoint_dir: Optional[str], video_ref: str, output: str = "output_i2v
         upscale_height: int = 704, upscale_width: int = 1280, refine_num_inference_steps: int = 50, extend_windows: int = 0,
         num_cond_frames: int = 13, no_kv_cache: bool = False, refine_kv_cache: bool = False, context_parallel_size: int = 1,
         device: str = "cuda:0", dit_precision: str = "bf16", vae_precision: str = "bf16", flow_backend: str = "farneback",
-        components: Optional[dict] = None) -> LongCatRun:
+        components: Optional[dict] = None, text_encoder: str = "transformers") -> LongCatRun:
     """RUN:170-500 plus the continuation chain; see the module docstring.  components: any of {"vae", "scheduler", "dit"} to use
     instead of loading it from `checkpoint_dir` (tests: a synthetic DiT folder beside an injected VAE).  refine_num_inference_steps:
     the reference's fixed 50 (RUN:484), a keyword here so that the chain can be exercised at test sizes."""
@@ -158,6 +173,8 @@ def run(checkpoint_dir: Optional[str], video_ref: str, output: str = "output_i2v
         raise ValueError("--context_parallel_size must be 1: sequence parallelism is the `comm` of the modules and is not wired into this entry")
     if extend_windows < 0:
         raise ValueError("--extend-windows must be >= 0")
+    if text_encoder not in ("transformers", "native"):
+        raise ValueError(f"--text-encoder {text_encoder!r}: transformers or native")
     given = dict(components or {})
     if not {"vae", "scheduler", "dit"} <= set(given) or use_distill or enable_upscale:
         if checkpoint_dir is None or not os.path.isdir(checkpoint_dir):
@@ -195,8 +212,10 @@ def run(checkpoint_dir: Optional[str], video_ref: str, output: str = "output_i2v
         try:
             import transformers  # noqa: F401
         except ImportError as e:
-            raise ValueError("no --embeds file, and `transformers` is not importable to run the folder's text encoder") from e
-        emb = encode_with_transformers(checkpoint_dir, prompt or DEFAULT_PROMPT, negative_prompt if do_cfg else None, torch.device(device))
+            raise ValueError("no --embeds file, and `transformers` is not importable to run the folder's " +
+                             ("tokenizer" if text_encoder == "native" else "text encoder")) from e
+        encode = encode_native if text_encoder == "native" else encode_with_transformers
+        emb = encode(checkpoint_dir, prompt or DEFAULT_PROMPT, negative_prompt if do_cfg else None, torch.device(device))
     text = dict(prompt_embeds=emb["prompt_embeds"], prompt_attention_mask=emb["prompt_attention_mask"],
                 negative_prompt_embeds=emb.get("negative_prompt_embeds") if do_cfg else None,
                 negative_prompt_attention_mask=emb.get("negative_prompt_attention_mask") if do_cfg else None)
@@ -319,8 +338,18 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def cli_parser() -> argparse.ArgumentParser:
+    """build_parser() (the reference's arguments and the engine's own, pinned as a set by tests/test_longcat_checkpoint.py) plus
+    --text-encoder: what the command line parses."""
+    ap = build_parser()
+    ap.add_argument("--text-encoder", choices=["transformers", "native"], default="transformers",
+                    help="without --embeds: run the folder's UMT5 through the Hugging Face class (default) or on this engine's own kernels "
+                         "(worldforge_amd/umt5.py; the tokenizer still comes from transformers)")
+    return ap
+
+
 def main(argv=None):
-    a = build_parser().parse_args(argv)
+    a = cli_parser().parse_args(argv)
     for flag, on in (("--enable_compile", a.enable_compile), ("--fps", a.fps != 15), ("--scene", a.scene is not None)):
         if on:
             print(f"note: {flag} is accepted and ignored" + (" (pass --prompt)" if flag == "--scene" else ""))
@@ -332,7 +361,8 @@ def main(argv=None):
             use_pca_channel_selection=a.use_pca_channel_selection, static=a.static == "True", max_replace=a.max_replace, save_png=a.save_png,
             enable_upscale=a.enable_upscale, t_thresh=a.t_thresh, upscale_height=a.upscale_height, upscale_width=a.upscale_width,
             extend_windows=a.extend_windows, num_cond_frames=a.num_cond_frames, no_kv_cache=a.no_kv_cache, refine_kv_cache=a.refine_kv_cache,
-            context_parallel_size=a.context_parallel_size, device=a.device, dit_precision=a.dit_precision, vae_precision=a.vae_precision)
+            context_parallel_size=a.context_parallel_size, device=a.device, dit_precision=a.dit_precision, vae_precision=a.vae_precision,
+            text_encoder=a.text_encoder)
     print(f"{len(r.frames)} frames -> {r.png_dir}")
     if r.refined is not None:
         print(f"{len(r.refined)} refined frames -> {r.refined_png_dir}")
