@@ -1,8 +1,9 @@
-"""Digest of every way the LongCat DiT forward can run: for comparing two checkouts bit for bit and launch for launch.
+"""Digest of every way the LongCat and the Wan DiT forwards can run: for comparing two checkouts bit for bit and launch for launch.
 
-    python tools/longcat_forward_digest.py [--only PREFIX] [--dump DIR] > digest.txt
+    python tools/forward_digest.py [--only PREFIX] [--dump DIR] > digest.txt
 
-One seeded random model of the multirank tests' size runs each path on a small grid; per case (and per simulated rank) one line:
+One seeded random model of the multirank tests' size runs each path on a small grid (the Wan cases are named `wan.`...; `--only wan.`
+selects them); per case (and per simulated rank) one line:
 
     <case> out=<sha256> calls=<n> launches=<sha256> trace=<sha256>
 
@@ -28,6 +29,7 @@ import torch  # noqa: E402
 
 from tests.fakes import SimComm  # noqa: E402
 from worldforge_amd import _ffi  # noqa: E402
+from worldforge_amd.dit import DiTConfig, WanTransformer3DModel  # noqa: E402
 from worldforge_amd.longcat_dit import LongCatConfig, LongCatVideoTransformer3DModel  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -308,8 +310,96 @@ def _mxfp8():
     return _single(lambda: m.forward_tokens(x, ts, cap, mask, 1))
 
 
+# ---- the Wan DiT: the model and inputs of tests/test_gpu_multirank.py; every case traces TWO consecutive forwards (or CFG pairs), so that
+# the second one finds the prompt-context cache filled ----------------------------------------------------------------------------------
+def _wan_model(layers=2, **kw):
+    cfg = DiTConfig(dim=256, ffn_dim=512, num_heads=2, num_layers=layers, text_dim=64)
+    return WanTransformer3DModel(cfg, DEV, **kw).init_random(5)
+
+
+def _wan_inputs(T, Hh, Ww):
+    """-> latents, text, a second (shorter) text, image."""
+    return (_rand((36, T, Hh, Ww), 60).to(BF).to(DEV), _rand((30, 64), 61).to(BF).to(DEV), _rand((12, 64), 72).to(BF).to(DEV),
+            _rand((257, 1280), 62).to(BF).to(DEV))
+
+
+def _twice(fn):
+    return lambda: [fn(), fn()]
+
+
+def _env_ctx_cache_off(run):
+    """run() with WF_CTX_CACHE=0 (read by every forward; set around the whole case, simulated ranks included)."""
+    def wrapped():
+        old = os.environ.get("WF_CTX_CACHE")
+        os.environ["WF_CTX_CACHE"] = "0"
+        try:
+            return run()
+        finally:
+            os.environ.pop("WF_CTX_CACHE")
+            if old is not None:
+                os.environ["WF_CTX_CACHE"] = old
+    return wrapped
+
+
+def _wan_single(layers=2, pair=None, model_kw=None, **attrs):
+    """pair: None = forward_tokens, "tokens" = forward_tokens_pair, "cfg" = forward_cfg_pair, "call" = __call__ with a batch dimension."""
+    def run():
+        m = _wan_model(layers, **(model_kw or {}))
+        for k, v in attrs.items():
+            setattr(m, k, v)
+        x, text, text_b, img = _wan_inputs(3, 16, 20)
+        fn = {None: lambda: m.forward_tokens(x, 500.0, text, img),
+              "call": lambda: m(x[None], torch.tensor([500.0]), text[None], img[None])[0],
+              "tokens": lambda: m.forward_tokens_pair(x, 500.0, text, text_b, img),
+              "cfg": lambda: m.forward_cfg_pair(x[None], torch.tensor([500.0]), text[None], text_b[None], img[None])}[pair]
+        return _single(_twice(fn))
+    return run
+
+
+CASES["wan.default"] = _wan_single()
+CASES["wan.track_max"] = _wan_single(attn_track_max=True)
+CASES["wan.no_prescale"] = _wan_single(attn_prescale=False)
+CASES["wan.no_ctx_cache"] = _env_ctx_cache_off(_wan_single())
+CASES["wan.mxfp8"] = _wan_single(model_kw=dict(linear_precision="mxfp8"))
+CASES["wan.call"] = _wan_single(pair="call")
+CASES["wan.pair.share"] = _wan_single(3, "tokens", pair_share_layer0=True)
+CASES["wan.pair.no_share"] = _wan_single(3, "tokens", pair_share_layer0=False)
+CASES["wan.pair.share.no_ctx_cache"] = _env_ctx_cache_off(_wan_single(3, "tokens", pair_share_layer0=True))
+CASES["wan.pair.cfg_pair"] = _wan_single(3, "cfg")
+
+
+def _wan_ranks(P, thw, exchange, layers=2, pair=False, **attrs):
+    def run():
+        m0 = _wan_model(layers)
+        x, text, text_b, img = _wan_inputs(*thw)
+
+        def rank_fn(comm):
+            m = WanTransformer3DModel(m0.cfg, DEV, comm=comm)
+            m.w = m0.w
+            if exchange is not None:
+                m.exchange_mode, m.exchange_chunks = exchange
+            for k, v in attrs.items():
+                setattr(m, k, v)
+            if pair:
+                return _twice(lambda: [t.clone() for t in m.forward_tokens_pair(x, 500.0, text, text_b, img)])()
+            return _twice(lambda: m.forward_tokens(x, 500.0, text, img).clone())()
+
+        return [(f".rank{r}", out, trace) for r, (out, trace) in enumerate(_run_ranks(P, rank_fn))]
+    return run
+
+
+for _ex in (("gather", 1), ("chunked", 2), ("bcast", 1)):
+    for _P, _thw in ((2, (3, 16, 20)), (3, (5, 16, 24))):   # (2 layers at P = 3: rank 2 owns no context layer)
+        CASES[f"wan.ranks{_P}.{_ex[0]}{_ex[1]}"] = _wan_ranks(_P, _thw, _ex)
+    CASES[f"wan.ranks2.layers3.{_ex[0]}{_ex[1]}"] = _wan_ranks(2, (3, 16, 20), _ex, layers=3)   # (an uneven layer count per rank)
+CASES["wan.ranks2.no_ctx_cache"] = _env_ctx_cache_off(_wan_ranks(2, (3, 16, 20), None))
+CASES["wan.ranks2.pair.lockstep"] = _wan_ranks(2, (3, 16, 20), None, layers=3, pair=True)
+CASES["wan.ranks2.pair.sequential"] = _wan_ranks(2, (3, 16, 20), None, layers=3, pair=True, pair_lockstep=False)
+CASES["wan.ranks2.pair.lockstep.no_prescale"] = _wan_ranks(2, (3, 16, 20), None, layers=3, pair=True, attn_prescale=False)  # (-> "gather")
+
+
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap =argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--only", default="", help="run the cases whose name starts with this")
     ap.add_argument("--dump", default=None, help="folder for the full traces, one file per case")
     args = ap.parse_args()

@@ -26,7 +26,8 @@ import torch
 
 from . import _ffi, ops
 from ._ffi import WF_BF16, WF_F32, call
-from .forward_common import ForwardWorkspaces, run, wait_events
+from .forward_common import (ForwardWorkspaces, GatheredLayerKV, act, bf16_latents, gather_layer_kv, layers_per_rank, run,
+                             seeded_generators)
 
 EPI_BF16, EPI_BF16_GELU, EPI_F32, EPI_RESID, EPI_F32_ACC = 0, 1, 2, 3, 4
 
@@ -402,6 +403,89 @@ def expected_diffusers_state_dict(cfg: DiTConfig) -> Dict[str, tuple]:
     return out
 
 
+@dataclass(frozen=True, eq=False)
+class _ForwardPlan:
+    """Everything one forward derives from its arguments (WanTransformer3DModel._plan), fixed before its first launch; the names of
+    longcat_dit._ForwardPlan where the role is the same."""
+    tag: str                                    # separates the workspaces of concurrent forwards
+    T: int; Hh: int; Ww: int                    # noqa: E702  the latent frames and their size
+    n_layers: int                               # cfg.num_layers as this forward found it (a calibration run cuts the model down between forwards)
+    L_tok: int                                  # the tokens, over all ranks
+    L: int; lo: int                             # noqa: E702  this rank's rows, its first row's global index
+    Sp: int                                     # key rows of a shard = of a K workspace (whole 64-key tiles)
+    shard: object                               # parallel.ShardPlan, None without `comm`
+    cos: torch.Tensor; sin: torch.Tensor        # noqa: E702  RoPE tables of this rank's rows
+    prescale: bool; use_bounds: bool            # noqa: E702
+    scale: float; q_scale: float; sa_scale: float  # noqa: E702  1 / sqrt(head_dim); what the query producer folds in / the kernel is told
+    exchange: Optional[str]                     # the effective mode of the K / V^T exchange; None: this forward has none
+    consume: bool; produce: bool                # noqa: E702  this forward's role in a CFG pair that shares layer 0's self-attention block
+    share_ctx: bool                             # the prompt context's K / V^T are computed by rank i (mod P) and gathered
+
+
+class _PromptContext:
+    """The cross-attention keys / values of one forward's prompt context (WanTransformer3DModel._prompt_context): `layer(i)` hands out
+    layer i's operands from whichever source holds them.  entry: the context cache's entry of this (text, image) pair, None with
+    WF_CTX_CACHE=0.
+
+    Sequence-parallel jobs: the K / V of the prompt context (text 512 rows, image 257) are the same on every rank and do not shrink with
+    the token shard -- 3 % of a rank's GPU time at 8 ranks when every rank computes all 40 layers' (measured).  Each
+    rank computes the layers i = rank (mod P) only, the finished kernel operands ([H, rows, 128] keys, blocked V^T) are all-gathered
+    once per forward on the communication stream; layer i then reads slot [i % P][i // P].  Same kernels per layer: bit-identical.
+    With the context cache (default) this happens on the first forward of a prompt only: the gathered buffers ARE the cache entry."""
+
+    def __init__(self, model, pl, ws, emb, entry):
+        self.model, self.pl, self.ws, self.emb, self.entry = model, pl, ws, emb, entry
+        held = entry.get("shared") if pl.share_ctx and entry is not None else None
+        # (a held entry's events have long fired; waiting again costs nothing)
+        self.gathered = GatheredLayerKV(held.allb, held.P, held.events) if held is not None else None
+        self._to_gather = pl.share_ctx and held is None
+
+    def _operands(self, i, kc, vtc):
+        """The fused layout of layer i's prompt-context keys / values: rows [0, Li) image, [Li, Li + Lt) text."""
+        m, ws, emb, W, p, d = self.model, self.ws, self.emb, self.model._wl, f"blocks.{i}.", self.model.cfg.dim
+        Li, Lt, Lc = ws.Li, ws.Lt, ws.Lc
+        gemm(emb.ctx_i, W[p + "cross_attn.kv_img.w"], W[p + "cross_attn.kv_img.b"], ws.kvi, EPI_BF16)
+        m._heads(ws.kvi, 0, W[p + "cross_attn.norm_k_img"], None, None, kc[:, :Li], emb.n_img, lout=Lc)
+        m._vt(ws.kvi, d, vtc[:, :Li // 64], emb.n_img, hstride=Lc // 64)
+        gemm(emb.ctx_t, W[p + "cross_attn.kv.w"], W[p + "cross_attn.kv.b"], ws.kvt, EPI_BF16)
+        m._heads(ws.kvt, 0, W[p + "cross_attn.norm_k"], None, None, kc[:, Li:], Lt, lout=Lc)
+        m._vt(ws.kvt, d, vtc[:, Li // 64:], Lt, hstride=Lc // 64)
+
+    def launch_shared(self):
+        """Launch the shared gathers now (nothing to do when they are not wanted or the cache entry holds them).  Called once, right
+        after layer 0's K / V^T exchange has been launched: the context gathers queue BEHIND it on the communication stream (layer 0's
+        self-attention needs its keys first, the context is not read before layer 0's cross-attention)."""
+        if not self._to_gather:
+            return
+        m, pl, ws, bf = self.model, self.pl, self.ws, torch.bfloat16
+        _buf, H, P = m._tagged_buf(pl), m.cfg.num_heads, m.comm.world
+        nl = layers_per_rank(pl.n_layers, P)
+        loc = [_buf("ckvf_loc0", (nl, H, ws.Lc, 128), bf, zero=True), _buf("ckvf_loc1", (nl, H, ws.Lc // 64, 128, 64), bf)]
+        if self.entry is not None:   # cached entries own their buffers
+            allb = [torch.empty((P,) + tuple(t.shape), dtype=bf, device=m.device) for t in loc]
+        else:
+            allb = [_buf(f"ckvf_all{j}", (P,) + tuple(t.shape), bf) for j, t in enumerate(loc)]
+        self.gathered, self._to_gather = gather_layer_kv(pl.n_layers, m.comm, loc, allb, self._operands), False
+        if self.entry is not None:
+            self.entry["shared"] = self.gathered
+
+    def layer(self, i):
+        """-> (kc [H, Lc, 128], vtc [H, Lc / 64, 128, 64]) of layer i."""
+        if self.gathered is not None:
+            return self.gathered.layer(i)
+        if self.entry is None:   # no cache: this forward's own workspaces, computed in place
+            self._operands(i, self.ws.kc, self.ws.vtc)
+            return self.ws.kc, self.ws.vtc
+        # K / V of the text and image context depend on the prompt only, not on the latents or the timestep: computed on
+        # the first forward with a given (text, image) pair and kept (17 MB per layer) -- 130 forwards per video reuse them
+        if i not in self.entry:   # own buffers per layer
+            H, Lc, bf, dev = self.model.cfg.num_heads, self.ws.Lc, torch.bfloat16, self.model.device
+            kc, vtc = torch.zeros((H, Lc, 128), dtype=bf, device=dev), torch.empty((H, Lc // 64, 128, 64), dtype=bf, device=dev)
+            self._operands(i, kc, vtc)
+            self.entry[i] = (kc, vtc)
+        return self.entry[i]
+
+
 class WanTransformer3DModel(ForwardWorkspaces):
     dtype = torch.bfloat16
 
@@ -529,17 +613,9 @@ class WanTransformer3DModel(ForwardWorkspaces):
     def init_random(self, seed: int = 0):
         """Synthetic weights of the right shapes, generated directly on the device: there are no checkpoints
         offline.  Scaled so activations stay O(1) through 40 layers."""
-        cfg, dev = self.cfg, self.device
-        g = torch.Generator(device=dev).manual_seed(seed)
+        cfg = self.cfg
+        mat, vec = seeded_generators(self.device, seed)
         W = {}
-
-        def mat(n, k, std=None):
-            std = std if std is not None else 1.0 / math.sqrt(k)
-            return (torch.randn(n, k, generator=g, device=dev, dtype=torch.float32) * std).to(torch.bfloat16)
-
-        def vec(n, std=0.02, base=0.0):
-            return (torch.randn(n, generator=g, device=dev, dtype=torch.float32) * std + base).to(torch.bfloat16).float()
-
         d, f = cfg.dim, cfg.ffn_dim
         kp = cfg.in_dim * 4
         W["patch.w"], W["patch.b"] = mat(d, kp), vec(d)
@@ -610,19 +686,19 @@ class WanTransformer3DModel(ForwardWorkspaces):
     # ------------------------------------------------------------------------------------------------------------
     # forward
     # ------------------------------------------------------------------------------------------------------------
-    def _embed_condition(self, t_value: float, text: torch.Tensor, img: torch.Tensor, tag: str = ""):
+    def _embed_condition(self, pl, t_value: float, text: torch.Tensor, img: torch.Tensor):
         """model.py:546-563.  Returns e [1,dim] f32, e0 [6,dim] f32, ctx_text bf16 [512,dim], ctx_img bf16 [n_img,dim]."""
         cfg, W, dev = self.cfg, self.w, self.device
         bf, f32 = torch.bfloat16, torch.float32
-        _buf = lambda name, shape, dtype, zero=False: self._buf(name + tag, shape, dtype, zero)  # noqa: E731
+        _buf = self._tagged_buf(pl)
         sin = sinusoidal_embedding_1d(cfg.freq_dim, t_value).to(dev)
         t0 = _buf("t0", (1, cfg.dim), f32)
         gemm(ops.cast(sin, bf), W["time_embedding.0.w"], W["time_embedding.0.b"], t0, EPI_F32)
-        t0a = self._act(t0, None, bf, 0)
+        t0a = act(t0, None, bf, 0)
         e = _buf("e", (1, cfg.dim), f32)
         gemm(t0a, W["time_embedding.2.w"], W["time_embedding.2.b"], e, EPI_F32)
         e0 = _buf("e0", (1, 6 * cfg.dim), f32)
-        gemm(self._act(e, None, bf, 0), W["time_projection.1.w"], W["time_projection.1.b"], e0, EPI_F32)
+        gemm(act(e, None, bf, 0), W["time_projection.1.w"], W["time_projection.1.b"], e0, EPI_F32)
         # text: zero-pad to text_len rows (model.py:554-559), Linear -> GELU(tanh) -> Linear
         n_txt = text.shape[0]
         tx = _buf("txt_in", (cfg.text_len, cfg.text_dim), bf, zero=True)
@@ -640,17 +716,10 @@ class WanTransformer3DModel(ForwardWorkspaces):
         i1 = _buf("img_h", (n_img, cfg.img_dim), f32)
         gemm(i0, W["img_emb.proj.1.w"], W["img_emb.proj.1.b"], i1, EPI_F32)
         i2 = _buf("img_o", (n_img, cfg.dim), f32)
-        gemm(self._act(i1, None, bf, 1), W["img_emb.proj.3.w"], W["img_emb.proj.3.b"], i2, EPI_F32)
+        gemm(act(i1, None, bf, 1), W["img_emb.proj.3.w"], W["img_emb.proj.3.b"], i2, EPI_F32)
         ctx_i = _buf("ctx_i", (n_img, cfg.dim), bf)
         self._ln(i2, W["img_emb.proj.4.w"], W["img_emb.proj.4.b"], ctx_i, 1e-5, plus_one=False)
         return e, e0.view(6, cfg.dim), ctx_t, ctx_i
-
-    def _act(self, a, b, out_dtype, mode):
-        out = torch.empty(a.shape, dtype=out_dtype, device=a.device)
-        dt = {torch.float32: WF_F32, torch.bfloat16: WF_BF16}
-        call("wf_act", a.data_ptr(), dt[a.dtype], b.data_ptr() if b is not None else None, dt[b.dtype] if b is not None else 0,
-             out.data_ptr(), dt[out_dtype], mode, a.numel(), ops.stream())
-        return out
 
     def _ln(self, x, mul, add, out, eps, plus_one):
         L, C = x.shape
@@ -736,211 +805,215 @@ class WanTransformer3DModel(ForwardWorkspaces):
         point where another forward can usefully take over the compute stream).  `tag` separates the workspaces of concurrent
         forwards; the velocity lands in result[0].  share / role: the two forwards of a CFG pair (forward_tokens_pair) -- the "produce"
         forward copies its residual stream after layer 0's self-attention block into share["x"], the "consume" forward starts from it
-        instead of computing the patch embedding and that block again."""
-        cfg, W, dev = self.cfg, self._wl, self.device
-        _buf = lambda name, shape, dtype, zero=False: self._buf(name + tag, shape, dtype, zero)  # noqa: E731
-        bf, f32 = torch.bfloat16, torch.float32
+        instead of computing the patch embedding and that block again.
+
+        The stages are methods on one plan and one set of workspaces; self-attention is one method per path (_sa_*)."""
+        pl = self._plan(x_in, tag, mode, share, role)
+        W, eps = self._wl, self.cfg.eps
+        emb = self._embed(pl, x_in, t_value, text, img)
+        ws = self._workspaces(pl, emb.n_img)
+        ctx = self._prompt_context(pl, ws, emb, text, img)
+        x, emod = emb.x, ws.emod
+        for i in range(pl.n_layers):
+            p = f"blocks.{i}."
+            # e = modulation + e0 (model.py:298)
+            call("wf_act", W[p + "modulation"].data_ptr(), WF_F32, emb.e0.data_ptr(), WF_F32, emod.data_ptr(), WF_F32, 2,
+                 emod.numel(), ops.stream())
+            # ---- self-attention (model.py:302-306) ----
+            if i == 0 and pl.consume:
+                yield from self._sa_consume(pl, ctx, x, share)
+            else:
+                self._ln(x, emod[1], emod[0], ws.hbuf, eps, plus_one=True)
+                if pl.exchange is not None:
+                    yield from self._sa_exchange(pl, ws, ctx, i)
+                else:
+                    self._sa_local(pl, ws, i)
+                gemm(ws.ao, W[p + "self_attn.o.w"], W[p + "self_attn.o.b"], x, EPI_RESID, gate=emod[2])
+                if i == 0 and pl.produce:
+                    share["x"] = self._buf("x_pair_layer0", (pl.L, self.cfg.dim), torch.float32)
+                    share["x"].copy_(x)
+            self._cross_attention(pl, ws, emb, ctx, i)
+            self._ffn(ws, emb, i)
+        result[0] = self._head(pl, ws, emb)
+
+    def _plan(self, x_in, tag, mode, share, role) -> _ForwardPlan:
+        """Everything a forward derives from its arguments, before the first launch."""
+        cfg, comm = self.cfg, self.comm
         Cin, T, Hh, Ww = x_in.shape
         assert Cin == cfg.in_dim
-        f, h2, w2 = T, Hh // 2, Ww // 2
-        Lfull = f * h2 * w2
-        d, H = cfg.dim, cfg.num_heads
+        h2, w2 = Hh // 2, Ww // 2
+        L_tok = T * h2 * w2
         scale = 1.0 / math.sqrt(128.0)
         # self-attention: softmax_scale * log2(e) is folded into Q by its producer (in front of the one bf16 rounding) and the attention
         # kernel is told so with softmax_scale = 0 (k_attn_w4<4>: score accumulators start from -m)
         prescale = bool(self.attn_prescale)
         q_scale, sa_scale = (scale * 1.4426950408889634, 0.0) if prescale else (1.0, scale)
-        cos, sin = self._rope_tables(f, h2, w2)
-        e, e0, ctx_t, ctx_i = self._embed_condition(t_value, text, img, tag)
-        n_img = ctx_i.shape[0]
-        comm = self.comm
-        tok = _buf("tok", (Lfull, Cin * 4), bf)
-        call("wf_patchify", x_in.data_ptr(), tok.data_ptr(), Cin, T, Hh, Ww, ops.stream())
+        cos, sin = self._rope_tables(T, h2, w2)
         if comm is not None:
             # sequence parallelism: this rank owns a contiguous token shard; K / V^T are exchanged per layer (parallel.py)
             from .parallel import shard_plan
-            plan = shard_plan(Lfull, comm.world)
-            lo, hi = plan.bounds(comm.rank)
-            L, Lp = hi - lo, plan.shard_len
+            shard = shard_plan(L_tok, comm.world)
+            lo, hi = shard.bounds(comm.rank)
+            L, Sp = hi - lo, shard.shard_len
             if L <= 0:
                 raise ValueError(f"sequence-parallel plan leaves rank {comm.rank} of {comm.world} without tokens "
-                                 f"({Lfull} tokens in shards of {Lp}); use fewer ranks for this size")
-            tok, cos, sin = tok[lo:hi], cos[lo:hi], sin[lo:hi]
+                                 f"({L_tok} tokens in shards of {Sp}); use fewer ranks for this size")
+            # part launches are built for the pre-scaled-Q form
+            exchange = mode if prescale and comm.world > 1 else "gather"
         else:
-            plan = None
-            L, Lp = Lfull, _pad64(Lfull)
-
-        # patch embedding (model.py:534-537) as a GEMM -> fp32 residual stream
-        x = _buf("x", (L, d), f32)
-        consume = share is not None and role == "consume"
-        if not consume:
-            gemm(tok, W["patch.w"], W["patch.b"], x, EPI_F32)
-
-        hbuf = _buf("h", (L, d), bf)
-        qkv = _buf("qkv", (L, 3 * d), bf)
-        qh = _buf("qh", (H, L, 128), bf)
+            shard, lo, L, Sp, exchange = None, 0, L_tok, _pad64(L_tok), None
         # per-head max |k|^2 / |q|^2 (out of the producers' own pass: wf_rmsnorm_heads_bound) let the kernel drop its running-max tracking
         # when no score can overflow; attn_track_max withholds them (A/B)
-        use_bounds = prescale and not self.attn_track_max
-        qm = _buf("qmax2", (H,), f32) if use_bounds else None
-        ex = None
-        if comm is not None:
-            if not prescale or comm.world == 1:
-                mode = "gather"   # part launches are built for the pre-scaled-Q form
-            ex = self._exchange(tag, H, Lp, mode, int(self.exchange_chunks))
+        return _ForwardPlan(
+            tag=tag, T=T, Hh=Hh, Ww=Ww, n_layers=cfg.num_layers, L_tok=L_tok, L=L, lo=lo, Sp=Sp, shard=shard, cos=cos[lo:lo + L],
+            sin=sin[lo:lo + L], prescale=prescale, use_bounds=prescale and not self.attn_track_max, scale=scale, q_scale=q_scale,
+            sa_scale=sa_scale, exchange=exchange, consume=share is not None and role == "consume",
+            produce=share is not None and role == "produce", share_ctx=comm is not None and comm.world > 1)
+
+    def _embed(self, pl, x_in, t_value, text, img):
+        """Condition, patch embedding -> (e / e0: the time embedding and its six modulation rows, ctx_t / ctx_i / n_img: the embedded
+        prompt context, x: this rank's fp32 residual stream -- left for layer 0 to fill from the pair's producer when this forward consumes)."""
+        cfg, _buf = self.cfg, self._tagged_buf(pl)
+        e, e0, ctx_t, ctx_i = self._embed_condition(pl, t_value, text, img)
+        tok = _buf("tok", (pl.L_tok, cfg.in_dim * 4), torch.bfloat16)
+        call("wf_patchify", x_in.data_ptr(), tok.data_ptr(), cfg.in_dim, pl.T, pl.Hh, pl.Ww, ops.stream())
+        # patch embedding (model.py:534-537) as a GEMM -> fp32 residual stream
+        x = _buf("x", (pl.L, cfg.dim), torch.float32)
+        if not pl.consume:
+            gemm(tok[pl.lo:pl.lo + pl.L], self._wl["patch.w"], self._wl["patch.b"], x, EPI_F32)
+        return SimpleNamespace(e=e, e0=e0, ctx_t=ctx_t, ctx_i=ctx_i, n_img=ctx_i.shape[0], x=x)
+
+    def _workspaces(self, pl, n_img):
+        """Every per-layer workspace of this forward, and with it who holds the self-attention keys: `ex` (the exchange slots), or
+        kh / vt / km."""
+        cfg = self.cfg
+        bf, f32 = torch.bfloat16, torch.float32
+        d, H, L, Sp = cfg.dim, cfg.num_heads, pl.L, pl.Sp
+        _buf = self._tagged_buf(pl)
+        ws = SimpleNamespace(ex=None, kh=None, vt=None, km=None)
+        ws.hbuf = _buf("h", (L, d), bf)
+        ws.qkv = _buf("qkv", (L, 3 * d), bf)
+        ws.qh = _buf("qh", (H, L, 128), bf)
+        ws.qm = _buf("qmax2", (H,), f32) if pl.use_bounds else None
+        if pl.exchange is not None:
+            ws.ex = self._exchange(pl.tag, H, Sp, pl.exchange, int(self.exchange_chunks))
         else:
-            kh = _buf("kh", (H, Lp, 128), bf, zero=True)
-            vt = _buf("vt", (H, Lp // 64, 128, 64), bf)
-            km = _buf("kmax2", (H,), f32) if use_bounds else None
-        ao = _buf("ao", (L, d), bf)
-        qc = _buf("qc", (L, d), bf)
-        ffh = _buf("ffh", (L, ffn_padded_features(cfg.ffn_dim)), bf)
-        Lt, Li = cfg.text_len, _pad64(n_img)
+            ws.kh = _buf("kh", (H, Sp, 128), bf, zero=True)
+            ws.vt = _buf("vt", (H, Sp // 64, 128, 64), bf)
+            ws.km = _buf("kmax2", (H,), f32) if pl.use_bounds else None
+        ws.ao = _buf("ao", (L, d), bf)
+        ws.qc = _buf("qc", (L, d), bf)
+        ws.ffh = _buf("ffh", (L, ffn_padded_features(cfg.ffn_dim)), bf)
+        ws.Lt, ws.Li = cfg.text_len, _pad64(n_img)
         # the two cross-attentions of a layer (image context, then text context, summed: model.py:220-227) are ONE launch over a concatenated
         # key / value buffer [image tiles | text tiles] (wf_attn_cross2_fwd; bit-identical to two wf_attn_fwd launches: tests/test_gpu_dit.py)
-        Lc = Li + Lt
-        kvt = _buf("kvt", (cfg.text_len, 2 * d), bf)
-        kvi = _buf("kvi", (n_img, 2 * d), bf)
-        kc = _buf("kc", (H, Lc, 128), bf, zero=True)
-        vtc = _buf("vtc", (H, Lc // 64, 128, 64), bf)
-        emod = _buf("emod", (6, d), f32)
+        ws.Lc = ws.Li + ws.Lt
+        ws.kvt = _buf("kvt", (cfg.text_len, 2 * d), bf)
+        ws.kvi = _buf("kvi", (n_img, 2 * d), bf)
+        ws.kc = _buf("kc", (H, ws.Lc, 128), bf, zero=True)
+        ws.vtc = _buf("vtc", (H, ws.Lc // 64, 128, 64), bf)
+        ws.emod = _buf("emod", (6, d), f32)
+        return ws
 
-        def context_operands(pl, kc_, vtc_):
-            """The fused layout of one layer's prompt-context keys / values: rows [0, Li) image, [Li, Li + Lt) text."""
-            gemm(ctx_i, W[pl + "cross_attn.kv_img.w"], W[pl + "cross_attn.kv_img.b"], kvi, EPI_BF16)
-            self._heads(kvi, 0, W[pl + "cross_attn.norm_k_img"], None, None, kc_[:, :Li], n_img, lout=Lc)
-            self._vt(kvi, d, vtc_[:, :Li // 64], n_img, hstride=Lc // 64)
-            gemm(ctx_t, W[pl + "cross_attn.kv.w"], W[pl + "cross_attn.kv.b"], kvt, EPI_BF16)
-            self._heads(kvt, 0, W[pl + "cross_attn.norm_k"], None, None, kc_[:, Li:], Lt, lout=Lc)
-            self._vt(kvt, d, vtc_[:, Li // 64:], Lt, hstride=Lc // 64)
+    def _prompt_context(self, pl, ws, emb, text, img) -> _PromptContext:
+        return _PromptContext(self, pl, ws, emb, self._context_kv(text, img))
 
-        ctx_kv = self._context_kv(text, img)
-        # Sequence-parallel jobs: the K / V of the prompt context (text 512 rows, image 257) are the same on every rank and do not shrink with
-        # the token shard -- 3 % of a rank's GPU time at 8 ranks when every rank computes all 40 layers' (measured, DESIGN section 6).  Each
-        # rank computes the layers i = rank (mod P) only, the finished kernel operands ([H, rows, 128] keys, blocked V^T) are all-gathered
-        # once per forward on the communication stream; layer i then reads slot [i % P][i // P].  Same kernels per layer: bit-identical.
-        # With the context cache (default) this happens on the first forward of a prompt only: the gathered buffers ARE the cache entry.
-        ctx_shared = ctx_events = None
-        share_ctx = comm is not None and comm.world > 1
-        if share_ctx and ctx_kv is not None and "shared" in ctx_kv:
-            (ctx_shared, ctx_events), share_ctx = ctx_kv["shared"], False   # (the events have long fired; waiting again costs nothing)
+    # ---- self-attention, one method per path; the q / k / V^T producers in one place each ----------------------------------------
+    def _sa_queries(self, pl, ws, i):
+        """Normalised, rotated and (attn_prescale) pre-scaled queries of this rank's rows, with their norm bound."""
+        self._heads(ws.qkv, 0, self._wl[f"blocks.{i}.self_attn.norm_q"], pl.cos, pl.sin, ws.qh, pl.L, out_scale=pl.q_scale, bound=ws.qm)
 
-        def launch_context():
-            """Called once, right after layer 0's K / V^T exchange has been launched: the context gathers queue BEHIND it on the communication
-            stream (layer 0's self-attention needs its keys first, the context is not read before layer 0's cross-attention)."""
-            P_, nl = comm.world, (cfg.num_layers + comm.world - 1) // comm.world
-            mk = (lambda name, shape, zero=False: (torch.zeros if zero else torch.empty)(shape, dtype=bf, device=dev)) if ctx_kv is not None \
-                else (lambda name, shape, zero=False: _buf(name, shape, bf, zero))   # cached entries own their buffers
-            loc = [_buf("ckvf_loc0", (nl, H, Lc, 128), bf, zero=True), _buf("ckvf_loc1", (nl, H, Lc // 64, 128, 64), bf)]
-            allb = [mk(f"ckvf_all{j}", (P_,) + tuple(t.shape)) for j, t in enumerate(loc)]
-            for j in range(nl):
-                li = comm.rank + P_ * j
-                if li >= cfg.num_layers:
-                    break
-                context_operands(f"blocks.{li}.", loc[0][j], loc[1][j])
-            shared = ((allb, P_), [comm.all_gather_async(a_, l_) for a_, l_ in zip(allb, loc)])
-            if ctx_kv is not None:
-                ctx_kv["shared"] = shared
-            return shared
+    def _sa_keys(self, pl, ws, i, r0, r1, kh, vt, km):
+        """Rows [r0, r1) of this rank's as keys: K into kh, V^T into vt, the norm bound into km (None: not wanted)."""
+        d = self.cfg.dim
+        self._heads(ws.qkv[r0:r1], d, self._wl[f"blocks.{i}.self_attn.norm_k"], pl.cos[r0:r1], pl.sin[r0:r1], kh, r1 - r0, bound=km)
+        self._vt(ws.qkv[r0:r1], 2 * d, vt, r1 - r0)
 
-        for i in range(cfg.num_layers):
-            p = f"blocks.{i}."
-            # e = modulation + e0 (model.py:298)
-            call("wf_act", W[p + "modulation"].data_ptr(), WF_F32, e0.data_ptr(), WF_F32, emod.data_ptr(), WF_F32, 2,
-                 emod.numel(), ops.stream())
-            # ---- self-attention (model.py:302-306) ----
-            if i == 0 and consume:
-                # the other branch of the CFG pair has computed this block on the same latents and timestep: take its residual stream
-                if comm is not None:
-                    if share_ctx:      # this branch's prompt context, gathered behind the producer's layer-0 exchange
-                        ctx_shared, ctx_events = launch_context()
-                    yield i            # (lock-step: the producer runs one layer ahead; its copy is queued before this one resumes)
-                x.copy_(share["x"])
-            elif comm is None:
-                self._ln(x, emod[1], emod[0], hbuf, cfg.eps, plus_one=True)
-                gemm(hbuf, W[p + "qkv.w"], W[p + "qkv.b"], qkv, EPI_BF16)
-                self._heads(qkv, 0, W[p + "self_attn.norm_q"], cos, sin, qh, L, out_scale=q_scale, bound=qm)
-                self._heads(qkv, d, W[p + "self_attn.norm_k"], cos, sin, kh, L, bound=km)
-                self._vt(qkv, 2 * d, vt, L)
-                attention(qh, kh, vt, ao, L, sa_scale, profile=True, kmax2=km, qmax2=qm)
-            else:
-                self._ln(x, emod[1], emod[0], hbuf, cfg.eps, plus_one=True)
-                # K and V first: the producers write this rank's shard (and its norm bounds) straight into its slot of the exchange
-                # buffers, chunk by chunk; the exchange runs on the communication stream under the Q projection
-                gemm(hbuf, W[p + "qkv.w"][d:], W[p + "qkv.b"][d:], qkv[:, d:], EPI_BF16)
-                for g in range(ex.G):
-                    r0, r1 = ex.chunk_rows(g, L)
-                    if r1 > r0:
-                        self._heads(qkv[r0:r1], d, W[p + "self_attn.norm_k"], cos[r0:r1], sin[r0:r1], ex.own_k(g), r1 - r0,
-                                    bound=ex.own_km(g) if use_bounds else None)
-                        self._vt(qkv[r0:r1], 2 * d, ex.own_vt(g), r1 - r0)
-                ex.launch()
-                if i == 0 and share_ctx:
-                    ctx_shared, ctx_events = launch_context()
-                yield i
-                gemm(hbuf, W[p + "qkv.w"][:d], W[p + "qkv.b"][:d], qkv[:, :d], EPI_BF16)
-                self._heads(qkv, 0, W[p + "self_attn.norm_q"], cos, sin, qh, L, out_scale=q_scale, bound=qm)
-                attention_exchange(qh, ex, ao, Lfull, sa_scale, qm, use_bounds=use_bounds, profile=True)
-            if not (i == 0 and consume):
-                gemm(ao, W[p + "self_attn.o.w"], W[p + "self_attn.o.b"], x, EPI_RESID, gate=emod[2])
-            if i == 0 and share is not None and role == "produce":
-                share["x"] = self._buf("x_pair_layer0", (L, d), f32)
-                share["x"].copy_(x)
-            # ---- cross-attention (model.py:310, 202-229) ----
-            self._ln(x, W[p + "norm3.w"], W[p + "norm3.b"], hbuf, cfg.eps, plus_one=False)
-            gemm(hbuf, W[p + "cross_attn.q.w"], W[p + "cross_attn.q.b"], qc, EPI_BF16)
-            self._heads(qc, 0, W[p + "cross_attn.norm_q"], None, None, qh, L)
-            # K / V of the text and image context depend on the prompt only, not on the latents or the timestep: computed on
-            # the first forward with a given (text, image) pair and kept (17 MB per layer) -- 130 forwards per video reuse them
-            kv = ctx_kv.get(i) if ctx_kv is not None else None
-            if ctx_shared is not None:
-                if ctx_events is not None:  # first use: the gathers were launched before layer 0
-                    wait_events(ctx_events)
-                    ctx_events = None
-                allb, P_ = ctx_shared
-                kc, vtc = (a_[i % P_, i // P_] for a_ in allb)
-            elif kv is None:
-                if ctx_kv is not None:  # own buffers per layer
-                    kc, vtc = torch.zeros((H, Lc, 128), dtype=bf, device=dev), torch.empty((H, Lc // 64, 128, 64), dtype=bf, device=dev)
-                context_operands(p, kc, vtc)
-                if ctx_kv is not None:
-                    ctx_kv[i] = (kc, vtc)
-            else:
-                kc, vtc = kv
-            cross_attention2(qh, kc, vtc, ao, Li, n_img, Lt, scale)
-            gemm(ao, W[p + "cross_attn.o.w"], W[p + "cross_attn.o.b"], x, EPI_RESID, gate=None)
-            # ---- FFN (model.py:311-313) ----
-            self._ln(x, emod[4], emod[3], hbuf, cfg.eps, plus_one=True)
-            gemm(hbuf, W[p + "ffn.0.w"], W[p + "ffn.0.b"], ffh, EPI_BF16_GELU)
-            gemm(ffh[:, :cfg.ffn_dim], W[p + "ffn.2.w"], W[p + "ffn.2.b"], x, EPI_RESID, gate=emod[5])
+    def _sa_local(self, pl, ws, i):
+        """One GPU: keys in this forward's own workspaces."""
+        W, p = self._wl, f"blocks.{i}."
+        gemm(ws.hbuf, W[p + "qkv.w"], W[p + "qkv.b"], ws.qkv, EPI_BF16)
+        self._sa_queries(pl, ws, i)
+        self._sa_keys(pl, ws, i, 0, pl.L, ws.kh, ws.vt, ws.km)
+        attention(ws.qh, ws.kh, ws.vt, ws.ao, pl.L, pl.sa_scale, profile=True, kmax2=ws.km, qmax2=ws.qm)
 
-        # ---- head (model.py:337-347) + unpatchify (:584-607) ----
-        hm = _buf("hm", (2, d), f32)
+    def _sa_exchange(self, pl, ws, ctx, i):
+        """Sequence parallel; yields once, right after the exchange has been launched."""
+        W, p, d, ex = self._wl, f"blocks.{i}.", self.cfg.dim, ws.ex
+        # K and V first: the producers write this rank's shard (and its norm bounds) straight into its slot of the exchange
+        # buffers, chunk by chunk; the exchange runs on the communication stream under the Q projection
+        gemm(ws.hbuf, W[p + "qkv.w"][d:], W[p + "qkv.b"][d:], ws.qkv[:, d:], EPI_BF16)
+        for g in range(ex.G):
+            r0, r1 = ex.chunk_rows(g, pl.L)
+            if r1 > r0:
+                self._sa_keys(pl, ws, i, r0, r1, ex.own_k(g), ex.own_vt(g), ex.own_km(g) if pl.use_bounds else None)
+        ex.launch()
+        if i == 0:
+            ctx.launch_shared()
+        yield i
+        gemm(ws.hbuf, W[p + "qkv.w"][:d], W[p + "qkv.b"][:d], ws.qkv[:, :d], EPI_BF16)
+        self._sa_queries(pl, ws, i)
+        attention_exchange(ws.qh, ex, ws.ao, pl.L_tok, pl.sa_scale, ws.qm, use_bounds=pl.use_bounds, profile=True)
+
+    def _sa_consume(self, pl, ctx, x, share):
+        """Layer 0 of a CFG pair's second branch: the other branch has computed this block on the same latents and timestep; take its
+        residual stream."""
+        if pl.exchange is not None:
+            ctx.launch_shared()   # this branch's prompt context, gathered behind the producer's layer-0 exchange
+            yield 0               # (lock-step: the producer runs one layer ahead; its copy is queued before this one resumes)
+        x.copy_(share["x"])
+
+    def _cross_attention(self, pl, ws, emb, ctx, i):
+        """model.py:310, 202-229."""
+        W, p, x = self._wl, f"blocks.{i}.", emb.x
+        self._ln(x, W[p + "norm3.w"], W[p + "norm3.b"], ws.hbuf, self.cfg.eps, plus_one=False)
+        gemm(ws.hbuf, W[p + "cross_attn.q.w"], W[p + "cross_attn.q.b"], ws.qc, EPI_BF16)
+        self._heads(ws.qc, 0, W[p + "cross_attn.norm_q"], None, None, ws.qh, pl.L)
+        kc, vtc = ctx.layer(i)
+        cross_attention2(ws.qh, kc, vtc, ws.ao, ws.Li, emb.n_img, ws.Lt, pl.scale)
+        gemm(ws.ao, W[p + "cross_attn.o.w"], W[p + "cross_attn.o.b"], x, EPI_RESID, gate=None)
+
+    def _ffn(self, ws, emb, i):
+        """model.py:311-313."""
+        cfg, W, p, x = self.cfg, self._wl, f"blocks.{i}.", emb.x
+        self._ln(x, ws.emod[4], ws.emod[3], ws.hbuf, cfg.eps, plus_one=True)
+        gemm(ws.hbuf, W[p + "ffn.0.w"], W[p + "ffn.0.b"], ws.ffh, EPI_BF16_GELU)
+        gemm(ws.ffh[:, :cfg.ffn_dim], W[p + "ffn.2.w"], W[p + "ffn.2.b"], x, EPI_RESID, gate=ws.emod[5])
+
+    def _head(self, pl, ws, emb):
+        """Head (model.py:337-347) + unpatchify (:584-607) -> velocity [out_dim, T, Hh, Ww] fp32."""
+        cfg, W, d = self.cfg, self._wl, self.cfg.dim
+        _buf = self._tagged_buf(pl)
+        hm = _buf("hm", (2, d), torch.float32)
         # head modulation (model.py:345): hm[r] = modulation[r] + e
         for r in range(2):
-            call("wf_act", W["head.modulation"][r].data_ptr(), WF_F32, e.data_ptr(), WF_F32, hm[r].data_ptr(), WF_F32, 2, d,
+            call("wf_act", W["head.modulation"][r].data_ptr(), WF_F32, emb.e.data_ptr(), WF_F32, hm[r].data_ptr(), WF_F32, 2, d,
                  ops.stream())
-        self._ln(x, hm[1], hm[0], hbuf, cfg.eps, plus_one=True)
-        y = _buf("y", (L, 4 * cfg.out_dim), f32)
-        gemm(hbuf, W["head.head.w"], W["head.head.b"], y, EPI_F32)
-        if comm is not None:
+        self._ln(emb.x, hm[1], hm[0], ws.hbuf, cfg.eps, plus_one=True)
+        y_own = _buf("y", (pl.L, 4 * cfg.out_dim), torch.float32)
+        gemm(ws.hbuf, W["head.head.w"], W["head.head.b"], y_own, EPI_F32)
+        if self.comm is None:
+            y = y_own
+        else:
             from .parallel import gather_rows
-            y = gather_rows(comm, y, plan).contiguous()
-        out = torch.empty((cfg.out_dim, T, Hh, Ww), dtype=f32, device=dev)
-        call("wf_unpatchify", y.data_ptr(), out.data_ptr(), cfg.out_dim, T, Hh, Ww, ops.stream())
-        result[0] = out
+            y = gather_rows(self.comm, y_own, pl.shard).contiguous()
+        out = torch.empty((cfg.out_dim, pl.T, pl.Hh, pl.Ww), dtype=torch.float32, device=self.device)
+        call("wf_unpatchify", y.data_ptr(), out.data_ptr(), cfg.out_dim, pl.T, pl.Hh, pl.Ww, ops.stream())
+        return out
+
+    def _batch1(self, refusal, hidden_states, timestep, *embeds):
+        """The diffusers-style batch of ONE sample -> x [in_dim, T, h, w], the timestep as a host float and embeds[j][0], all tensors
+        bf16 and contiguous as forward_tokens takes them."""
+        if hidden_states.shape[0] != 1:
+            raise NotImplementedError(refusal)
+        t_value = float(torch.as_tensor(timestep).reshape(-1)[0].item())
+        return (bf16_latents(hidden_states[0]), t_value) + tuple(e[0].to(torch.bfloat16).contiguous() for e in embeds)
 
     def __call__(self, hidden_states: torch.Tensor, timestep, encoder_hidden_states: torch.Tensor,
                  encoder_hidden_states_image: Optional[torch.Tensor] = None, attention_kwargs=None, return_dict: bool = False):
-        if hidden_states.shape[0] != 1:
-            raise NotImplementedError("batch size 1 (the reference path); run CFG branches as separate calls")
-        t_value = float(torch.as_tensor(timestep).reshape(-1)[0].item())
-        x = hidden_states[0]
-        if x.dtype != torch.bfloat16:
-            x = ops.cast(x.contiguous(), torch.bfloat16)
-        v = self.forward_tokens(x.contiguous(), t_value, encoder_hidden_states[0].to(torch.bfloat16).contiguous(),
-                                encoder_hidden_states_image[0].to(torch.bfloat16).contiguous())
-        out = ops.cast(v, self.dtype).unsqueeze(0)
+        x, t_value, text, img = self._batch1("batch size 1 (the reference path); run CFG branches as separate calls", hidden_states, timestep,
+                                             encoder_hidden_states, encoder_hidden_states_image)
+        out = ops.cast(self.forward_tokens(x, t_value, text, img), self.dtype).unsqueeze(0)
         if return_dict:
             return SimpleNamespace(sample=out)
         return (out,)
@@ -949,13 +1022,7 @@ class WanTransformer3DModel(ForwardWorkspaces):
                          negative_encoder_hidden_states: torch.Tensor, encoder_hidden_states_image: torch.Tensor):
         """Both transformer calls of PIPE:593-610 (positive, then negative prompt) -> (noise_pred, noise_uncond), each what
         __call__(...)[0] returns.  See forward_tokens_pair."""
-        if hidden_states.shape[0] != 1:
-            raise NotImplementedError("batch size 1 (the reference path)")
-        t_value = float(torch.as_tensor(timestep).reshape(-1)[0].item())
-        x = hidden_states[0]
-        if x.dtype != torch.bfloat16:
-            x = ops.cast(x.contiguous(), torch.bfloat16)
-        img = encoder_hidden_states_image[0].to(torch.bfloat16).contiguous()
-        va, vb = self.forward_tokens_pair(x.contiguous(), t_value, encoder_hidden_states[0].to(torch.bfloat16).contiguous(),
-                                          negative_encoder_hidden_states[0].to(torch.bfloat16).contiguous(), img)
+        x, t_value, text, neg, img = self._batch1("batch size 1 (the reference path)", hidden_states, timestep, encoder_hidden_states,
+                                                  negative_encoder_hidden_states, encoder_hidden_states_image)
+        va, vb = self.forward_tokens_pair(x, t_value, text, neg, img)
         return ops.cast(va, self.dtype).unsqueeze(0), ops.cast(vb, self.dtype).unsqueeze(0)

@@ -43,10 +43,11 @@ import numpy as np
 import torch
 
 from . import ops
-from ._ffi import WF_BF16, WF_F32, call
+from ._ffi import call
 from .dit import (EPI_BF16, EPI_BF16_GELU, EPI_F32, EPI_F32_ACC, _pad64, attention, attention_exchange, gemm, head_max_norm2,
                   quantize_linears)
-from .forward_common import ForwardWorkspaces, run, wait_events
+from .forward_common import (ForwardWorkspaces, act, bf16_latents, gather_layer_kv, layers_per_rank, run, seeded_generators,
+                             wait_events)
 
 
 @dataclass
@@ -544,17 +545,9 @@ class LongCatVideoTransformer3DModel(ForwardWorkspaces):
 
     def init_random(self, seed: int = 0):
         """Synthetic weights of the right shapes, generated on the device (there are no checkpoints offline)."""
-        cfg, dev = self.cfg, self.device
-        g = torch.Generator(device=dev).manual_seed(seed)
+        cfg = self.cfg
+        mat, vec = seeded_generators(self.device, seed)
         C, Ct, Hd = cfg.hidden_size, cfg.adaln_tembed_dim, cfg.ffn_hidden
-
-        def mat(n, k, std=None):
-            std = std if std is not None else 1.0 / math.sqrt(k)
-            return (torch.randn(n, k, generator=g, device=dev, dtype=torch.float32) * std).to(torch.bfloat16)
-
-        def vec(n, std=0.02, base=0.0):
-            return (torch.randn(n, generator=g, device=dev, dtype=torch.float32) * std + base).to(torch.bfloat16).float()
-
         W = {"patch.w": mat(C, cfg.in_channels * 4), "patch.b": vec(C)}
         for n, (o, i) in {"t_embedder.mlp.0": (Ct, cfg.frequency_embedding_size), "t_embedder.mlp.2": (Ct, Ct),
                           "y_embedder.y_proj.0": (C, cfg.caption_channels), "y_embedder.y_proj.2": (C, C),
@@ -579,12 +572,6 @@ class LongCatVideoTransformer3DModel(ForwardWorkspaces):
 
     # ------------------------------------------------------------------------------------------------------------
     _rope_fn = staticmethod(rope_tables)  # (_buf, _exchange, _rope_tables: forward_common.ForwardWorkspaces)
-
-    def _act(self, a, out_dtype, mode):
-        out = torch.empty(a.shape, dtype=out_dtype, device=a.device)
-        dt = {torch.float32: WF_F32, torch.bfloat16: WF_BF16}
-        call("wf_act", a.data_ptr(), dt[a.dtype], None, 0, out.data_ptr(), dt[out_dtype], mode, a.numel(), ops.stream())
-        return out
 
     def _gemm_f32(self, a: torch.Tensor, w, b, out):
         """out f32 = a f32 @ w^T + b with the fp32 activation split into a hi + lo bf16 pair (two MFMA GEMMs accumulating in fp32):
@@ -809,9 +796,6 @@ class LongCatVideoTransformer3DModel(ForwardWorkspaces):
             sparsity=sparsity, cdf_thr=cdf_thr,
             fused_sel=not os.environ.get("WF_BSA_TORCH_SELECT"))  # (the env switch keeps the torch selection paths testable)
 
-    def _tagged_buf(self, pl):
-        return lambda name, shape, dtype, zero=False: self._buf(name + pl.tag, shape, dtype, zero)
-
     def _embed(self, pl, x_in, timesteps, caption, caption_mask):
         """Patch, timestep and caption embeddings -> (x: this rank's residual stream, ada / ald: the AdaLN parameters of all blocks and
         their row stride, fmod: the final layer's, y / n_txt: the caption tokens); a build has no caption and no final layer."""
@@ -829,8 +813,8 @@ class LongCatVideoTransformer3DModel(ForwardWorkspaces):
         gemm(tok[pl.lo:pl.lo + pl.L], W["patch.w"], W["patch.b"], x, EPI_BF16)  # LCB:112 (Conv3d with kernel = stride = patch)
         tf = timestep_embedding(timesteps, cfg.frequency_embedding_size).to(dev)  # LCB:201-206
         t0 = self._gemm_f32(tf, W["t_embedder.mlp.0.w"], W["t_embedder.mlp.0.b"], _buf("t0", (T, Ct), f32))
-        t = self._gemm_f32(self._act(t0, f32, 0), W["t_embedder.mlp.2.w"], W["t_embedder.mlp.2.b"], _buf("t", (T, Ct), f32))
-        st = self._act(t, f32, 0)  # SiLU(t), shared by every adaLN_modulation (LCD:40-43, LCB:156)
+        t = self._gemm_f32(act(t0, None, f32, 0), W["t_embedder.mlp.2.w"], W["t_embedder.mlp.2.b"], _buf("t", (T, Ct), f32))
+        st = act(t, None, f32, 0)  # SiLU(t), shared by every adaLN_modulation (LCD:40-43, LCB:156)
         ada = self._gemm_f32(st, W["ada.w"], W["ada.b"], _buf("ada", (T, W["ada.w"].shape[0]), f32))   # (all stored blocks: a run on the first cfg.depth blocks only reads its own columns)
         fmod, y, n_txt = None, None, 0
         if not pl.build:
@@ -902,22 +886,17 @@ class LongCatVideoTransformer3DModel(ForwardWorkspaces):
 
     def _shared_caption_kv(self, pl, ws, emb):
         """Sequence-parallel jobs: the caption K / V^T of layer i are computed by rank i (mod P) only and all-gathered once per forward
-        (see dit.py: work that does not shrink with the token shard).  -> None, or the gathered buffers with the events of their
-        gathers, which the first cross-attention waits for."""
+        (see dit.py: work that does not shrink with the token shard).  -> None, or the gathered buffers
+        (forward_common.GatheredLayerKV), whose first use by a cross-attention waits for the gathers."""
         cfg, comm = self.cfg, self.comm
         if comm is None or comm.world <= 1:
             return None
         bf, H, Ltp = torch.bfloat16, cfg.num_heads, _pad64(emb.n_txt)
         _buf = self._tagged_buf(pl)
-        P_, nl = comm.world, (cfg.depth + comm.world - 1) // comm.world
+        nl = layers_per_rank(cfg.depth, comm.world)
         loc = [_buf("ckv_loc0", (nl, H, Ltp, 128), bf, zero=True), _buf("ckv_loc1", (nl, H, Ltp // 64, 128, 64), bf)]
-        allb = [_buf(f"ckv_all{j}", (P_,) + tuple(t.shape), bf) for j, t in enumerate(loc)]
-        for j in range(nl):
-            i = comm.rank + P_ * j
-            if i >= cfg.depth:
-                break
-            self._caption_kv(ws, emb, i, loc[0][j], loc[1][j])
-        return SimpleNamespace(allb=allb, P=P_, events=[comm.all_gather_async(a_, l_) for a_, l_ in zip(allb, loc)])
+        allb = [_buf(f"ckv_all{j}", (comm.world,) + tuple(t.shape), bf) for j, t in enumerate(loc)]
+        return gather_layer_kv(cfg.depth, comm, loc, allb, lambda i, kth, vtt: self._caption_kv(ws, emb, i, kth, vtt))
 
     # ---- self-attention, one method per path; each decides in ONE place whose K / V^T / bound it runs on ------------------------
     def _sa_queries(self, pl, ws, i):
@@ -1067,10 +1046,7 @@ class LongCatVideoTransformer3DModel(ForwardWorkspaces):
         gemm(ws.hbuf[nc:], W[p + "cross_attn.q_linear.w"], W[p + "cross_attn.q_linear.b"], ws.qc[nc:], EPI_BF16)
         self._heads(ws.qc, 0, W[p + "cross_attn.q_norm"], None, None, ws.qh_n, nc, L)
         if ctx is not None:
-            if ctx.events is not None:
-                wait_events(ctx.events)
-                ctx.events = None
-            kth_i, vtt_i = (a_[i % ctx.P, i // ctx.P] for a_ in ctx.allb)
+            kth_i, vtt_i = ctx.layer(i)
         else:
             self._caption_kv(ws, emb, i, ws.kth, ws.vtt)
             kth_i, vtt_i = ws.kth, ws.vtt
@@ -1107,11 +1083,8 @@ class LongCatVideoTransformer3DModel(ForwardWorkspaces):
             cap = cap[:, 0]
         samples = []
         for b in range(B):
-            x = hidden_states[b]
-            if x.dtype != torch.bfloat16:
-                x = ops.cast(x.contiguous(), torch.bfloat16)
             mask = encoder_attention_mask[b] if encoder_attention_mask is not None else None
-            samples.append((x.contiguous(), ts[b].tolist(), cap[b].to(torch.bfloat16).contiguous(), mask))
+            samples.append((bf16_latents(hidden_states[b]), ts[b].tolist(), cap[b].to(torch.bfloat16).contiguous(), mask))
         return samples
 
     # ---- video continuation on a resident condition cache (LCA:147-181, PIPE:336-348) --------------------------------------------
