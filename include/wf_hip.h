@@ -401,6 +401,28 @@ int wf_t5_rmsnorm(const float* x, const float* weight, void* out, int L, int C, 
  * exact.  The host refuses ids outside [0, V) (ValueError) before the call; the kernel clamps and never reads outside the table. */
 int wf_t5_embed(const int* ids, const void* table, float* out, int L, int V, int C, void* stream);
 
+/* ---- CLIP vision encoder (csrc/clip.hip; HF transformers/models/clip/modeling_clip.py: CLIPVisionModel, which the reference loads in
+ *      float32; worldforge_amd/clip.py is the host).  Everything is fp32 on the fp32-input MFMA (v_mfma_f32_32x32x2_f32): no operand and no
+ *      partial result is narrower than fp32.  The LayerNorms are wf_ln_modulate with plus_one = 0 and WF_F32 output. ---- */
+#define WF_EPI_F32_GELU 5        /* out f32 = 0.5 v (1 + erf(v / sqrt 2)), v = acc + bias        (hidden_act "gelu") */
+#define WF_EPI_F32_QUICK_GELU 6  /* out f32 = v * sigmoid(1.702 v)                                (hidden_act "quick_gelu") */
+/* out[M,N] = epi(X[M,K] . W[N,K]^T + bias), every operand fp32 (row strides ldx, ldw, ldo in elements), each dot product a chain of fp32
+ * fma in a fixed order that depends on K alone: two calls give the same bits, no atomics.  epilogue WF_EPI_F32, WF_EPI_F32_ACC (out +=),
+ * WF_EPI_F32_GELU or WF_EPI_F32_QUICK_GELU; bias f32 [N] or NULL.  Any M >= 1; K % 4 == 0, N % 4 == 0, leading dimensions % 4, 16-byte
+ * aligned pointers; anything else returns WF_EINVAL before any device work. */
+int wf_gemm_f32(const float* X, const float* W, const float* bias, float* out, int M, int N, int K, int ldx, int ldw, int ldo, int epilogue,
+                void* stream);
+/* CLIPAttention.forward without a mask: O = softmax_j(scale * q_i . k_j) V per head, fp32 in and out.  Q, K, V are three column slices of
+ * one stacked [L, ldqkv] buffer with head h at columns h * D; O [L, ldo].  The scores, the exact row maximum, p = exp(s - max), the row sum
+ * and both products are fp32 (p is never rounded below fp32); the output is acc / sum.  Two calls give the same bits.  WF_EINVAL before
+ * any device work unless D % 8 == 0, 8 <= D <= 128, 1 <= L <= 1024, 1 <= H <= 65535, ldqkv % 4 == 0, ldo % 4 == 0, both >= H * D, scale
+ * positive and finite, 16-byte aligned pointers. */
+int wf_clip_attn_fwd(const float* Q, const float* K, const float* V, int ldqkv, float* O, int ldo, int H, int L, int D, float scale,
+                     void* stream);
+/* CLIPVisionEmbeddings.patch_embedding (a Conv2d with kernel = stride = p and no bias) as a GEMM operand: pixels f32 [3][S][S] -> rows f32
+ * [G * G][3 * p * p], G = S / p, row py * G + px, column c * p * p + ph * p + pw (the flattening order of the conv weight): a copy, exact. */
+int wf_clip_patch_rows(const float* pixels, float* rows, int S, int p, void* stream);
+
 /* ---- 3D causal VAE (wan/modules/vae.py; the in-tree statement of diffusers' AutoencoderKLWan), channels-last ----------- */
 /* CausalConv3d / Conv2d as implicit GEMM on MFMA (vae.py:17-36, 76-96, 186-220).  in bf16 [Ti,Hi,Wi,Cin] (Cin % 32 == 0),
  * w bf16 [Cout][kt*kh*kw][Cin], bias f32; out (f32 and/or bf16) [To,Ho,Wo,Cout] (+ resid f32 of the same shape).

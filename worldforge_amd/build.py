@@ -37,6 +37,7 @@ SOURCES = {
     "dit_ops.hip": [],
     "longcat_ops.hip": ["-ffp-contract=off"],
     "t5.hip": [],
+    "clip.hip": [],
     "vae_ops.hip": [],
     "conv.hip": [],
     "warp.hip": ["-ffp-contract=off"],

@@ -7,7 +7,7 @@ data_offsets}}, then the raw little-endian tensor bytes) and memory-mapped, so a
 host more than once per tensor on its way to HBM.  No dependency on the `safetensors` package (tests use it as the writer).
 
 `audit(path)` / `python -m worldforge_amd.checkpoint PATH [--json]` say what a checkpoint folder lacks BEFORE anything is loaded: per
-component (`dit/` LongCat, `transformer/` Wan, `vae/`, `text_encoder/`, `scheduler/`, `lora/*.safetensors`) the keys the loader needs and the folder
+component (`dit/` LongCat, `transformer/` Wan, `vae/`, `text_encoder/`, `image_encoder/`, `scheduler/`, `lora/*.safetensors`) the keys the loader needs and the folder
 lacks, the keys no loader consumes, wrong shapes, dtypes, bytes and the consistency of a shard index.  It reads safetensors HEADERS and
 JSON files only, never tensor data, and touches no GPU."""
 from __future__ import annotations
@@ -281,6 +281,30 @@ def _audit_text_encoder(folder: str) -> dict:
     return c
 
 
+def _audit_image_encoder(folder: str) -> dict:
+    """clip.CLIPVisionModel.from_pretrained's header check: keys with or without the `vision_model.` prefix; the text tower and the
+    projections of a full CLIPModel file are noted, not counted; the last layer and post_layernorm are checked though never uploaded."""
+    from .clip import CLIPVisionConfig, consumed_header, expected_state_dict
+    c = _component("CLIPVisionModel", folder)
+    cj = _read_json(os.path.join(folder, "config.json"), c)
+    cfg = None
+    if cj is None:
+        if not c["refused"]:
+            c["missing"].append("config.json")
+    else:
+        try:
+            cfg = CLIPVisionConfig.from_dict(cj)
+        except (NotImplementedError, ValueError, TypeError) as e:
+            c["refused"].append(str(e))
+    found = _fill_header(c, folder)
+    if found is not None and cfg is not None:
+        keep, dropped, _ = consumed_header(found)
+        if dropped:
+            c["notes"].append(f"{dropped} text_model.* / projection / logit_scale tensors are ignored by the vision encoder")
+        c["missing"], c["unexpected"], c["wrong_shape"] = compare_header(keep, expected_state_dict(cfg))
+    return c
+
+
 _SCHED_VALUES = ("shift", "flow_shift", "num_train_timesteps", "prediction_type", "solver_order")
 
 
@@ -384,6 +408,8 @@ def audit(path: str) -> dict:
         comps["vae"] = _audit_vae(os.path.join(path, "vae"))
     if os.path.isdir(os.path.join(path, "text_encoder")):
         comps["text_encoder"] = _audit_text_encoder(os.path.join(path, "text_encoder"))
+    if os.path.isdir(os.path.join(path, "image_encoder")):
+        comps["image_encoder"] = _audit_image_encoder(os.path.join(path, "image_encoder"))
     if os.path.isdir(os.path.join(path, "scheduler")):
         comps["scheduler"] = _audit_scheduler(os.path.join(path, "scheduler"), longcat="dit" in comps or "transformer" not in comps)
     for f in sorted(glob.glob(os.path.join(path, "lora", "*.safetensors"))):
@@ -397,7 +423,7 @@ def format_report(rep: dict, limit: int = 10) -> str:
     """The text report: per component the counts and at most `limit` names per class."""
     lines = [f"checkpoint {rep['path']}: {'OK' if rep['ok'] else 'PROBLEMS'}"]
     if not rep["components"]:
-        lines.append("  no component folder found (dit/, transformer/, vae/, text_encoder/, scheduler/, lora/*.safetensors)")
+        lines.append("  no component folder found (dit/, transformer/, vae/, text_encoder/, image_encoder/, scheduler/, lora/*.safetensors)")
     for name, c in rep["components"].items():
         dt = ", ".join(f"{k} x {v}" for k, v in sorted(c["dtypes"].items())) or "-"
         lines.append(f"  {name} ({c['kind']}): {sum(c['dtypes'].values())} tensors, {c['bytes'] / 2 ** 30:.3f} GiB, dtypes {dt}")

@@ -10,9 +10,10 @@
 Same argument names, defaults and meaning as the reference's CLI.  The UMT5 text encoder and the CLIP vision encoder run once per video and the
 loop consumes their outputs.  Those come in through --embeds (a .npz / .safetensors with `prompt_embeds` [1,L,4096], `negative_prompt_embeds`,
 `image_embeds` [1,257,1280]) or, when the checkpoint folder holds `text_encoder/`, `tokenizer/`, `image_encoder/`, `image_processor/` and
-`transformers` is importable, are computed with those classes exactly as PIPE:166-214 does (--text-encoder transformers, the default).
---text-encoder native runs the UMT5 weights on this engine's own kernels instead (worldforge_amd/umt5.py); the tokenizer and the CLIP vision
-encoder stay on `transformers` (the vision encoder is outside SURVEY section 8 and NOT re-implemented).
+`transformers` is importable, are computed with those classes exactly as PIPE:166-214 does (--text-encoder transformers --image-encoder
+transformers, the defaults).  --text-encoder native runs the UMT5 weights on this engine's own kernels instead (worldforge_amd/umt5.py) and
+--image-encoder native the CLIP vision weights, in float32 as the reference loads them (worldforge_amd/clip.py, with the image processor's PIL
+path restated on the host).  With both native, the only thing of `transformers` that is touched is the tokenizer (data plus a host library).
 The reference's scene -> prompt table (utils/prompts.py) is text data of the reference and is not shipped: pass --prompt; the negative
 prompt defaults to the entry point's own two literals (INFER:277-285, by --static).
 """
@@ -59,14 +60,15 @@ def encode_text_native(model_path: str, prompt: str, negative_prompt: str, devic
 
 
 def encode_with_transformers(model_path: str, prompt: str, negative_prompt: str, image, device, max_sequence_length: int = 512,
-                             text_encoder: str = "transformers"):
+                             text_encoder: str = "transformers", image_encoder: str = "transformers"):
     """PIPE:166-214 with the Hugging Face classes the reference itself uses (outside the hot path, once per video): UMT5 last_hidden_state
     truncated to each prompt's length and zero-padded to 512 rows (PIPE:190-199); CLIP vision hidden_states[-2] (PIPE:209-211).
-    text_encoder="native": the text half comes from encode_text_native; the CLIP vision encoder stays on `transformers`."""
-    from transformers import AutoTokenizer, CLIPImageProcessor, CLIPVisionModel, UMT5EncoderModel
+    text_encoder="native": the text half comes from encode_text_native.  image_encoder="native": image_embeds come from clip.encode_image
+    and neither CLIPVisionModel nor CLIPImageProcessor is imported; with both native only the tokenizer of `transformers` is used."""
     if text_encoder == "native":
         out = encode_text_native(model_path, prompt, negative_prompt, device, max_sequence_length)
     else:
+        from transformers import AutoTokenizer, UMT5EncoderModel
         tok = AutoTokenizer.from_pretrained(os.path.join(model_path, "tokenizer"), local_files_only=True)
         te = UMT5EncoderModel.from_pretrained(os.path.join(model_path, "text_encoder"), torch_dtype=torch.bfloat16, local_files_only=True).to(device)
         out = {}
@@ -78,6 +80,11 @@ def encode_with_transformers(model_path: str, prompt: str, negative_prompt: str,
                 h = te(t.input_ids.to(device), t.attention_mask.to(device)).last_hidden_state.to(torch.bfloat16)[0, :n]
             out[key] = torch.cat([h, h.new_zeros(max_sequence_length - n, h.shape[1])]).unsqueeze(0)
         del te
+    if image_encoder == "native":
+        from . import clip
+        out["image_embeds"] = clip.encode_image(model_path, image, device)
+        return out
+    from transformers import CLIPImageProcessor, CLIPVisionModel
     proc = CLIPImageProcessor.from_pretrained(os.path.join(model_path, "image_processor"), local_files_only=True)
     ie = CLIPVisionModel.from_pretrained(os.path.join(model_path, "image_encoder"), torch_dtype=torch.float32, local_files_only=True).to(device)
     with torch.no_grad():
@@ -92,7 +99,8 @@ def run(models_dir: Optional[str], video_ref: str, model: str = "720p", output: 
         prompt: Optional[str] = None, negative_prompt: Optional[str] = None, embeds: Optional[str] = None,
         use_pca_channel_selection: bool = False, soften_mask: bool = False, transition_distance: int = 15, decay_type: str = "sine",
         save_png: bool = False, device: str = "cuda:0", components: Optional[dict] = None, max_area: Optional[int] = None, seed: int = 42,
-        vae_precision: str = "fp16x3", flow_backend: str = "farneback", dit_precision: str = "bf16", text_encoder: str = "transformers"):
+        vae_precision: str = "fp16x3", flow_backend: str = "farneback", dit_precision: str = "bf16", text_encoder: str = "transformers",
+        image_encoder: str = "transformers"):
     """INFER:153-339.  Returns (frames float32 [F,H,W,3] in [0,1], output directory of the PNG frames or None).
     components: {"transformer", "vae", "scheduler"} to use instead of loading `models_dir` (tests; synthetic weights); max_area overrides the
     model's pixel budget the same way harness.prepare_inputs documents."""
@@ -103,6 +111,8 @@ def run(models_dir: Optional[str], video_ref: str, model: str = "720p", output: 
 
     if text_encoder not in ("transformers", "native"):
         raise ValueError(f"--text-encoder {text_encoder!r}: transformers or native")
+    if image_encoder not in ("transformers", "native"):
+        raise ValueError(f"--image-encoder {image_encoder!r}: transformers or native")
     dev = torch.device(device)
     model_path = None
     if components is None:
@@ -137,7 +147,7 @@ def run(models_dir: Optional[str], video_ref: str, model: str = "720p", output: 
     elif model_path is not None and all(os.path.isdir(os.path.join(model_path, d)) for d in ("text_encoder", "tokenizer", "image_encoder", "image_processor")):
         if prompt is None:
             raise ValueError("pass --prompt (the reference's scene -> prompt table utils/prompts.py is not shipped)")
-        emb = encode_with_transformers(model_path, prompt, negative_prompt, pil, dev, text_encoder=text_encoder)
+        emb = encode_with_transformers(model_path, prompt, negative_prompt, pil, dev, text_encoder=text_encoder, image_encoder=image_encoder)
     else:
         raise ValueError("no --embeds file and no text_encoder / image_encoder folders to compute them from")
 
@@ -185,6 +195,9 @@ def main(argv=None):
     ap.add_argument("--embeds", default=None, help=".npz / .safetensors with prompt_embeds, negative_prompt_embeds, image_embeds")
     ap.add_argument("--text-encoder", choices=["transformers", "native"], default="transformers",
                     help="without --embeds: run the folder's UMT5 through the Hugging Face class (default) or on this engine's own kernels")
+    ap.add_argument("--image-encoder", choices=["transformers", "native"], default="transformers",
+                    help="without --embeds: run the folder's CLIP vision encoder through the Hugging Face class (default) or on this engine's own "
+                         "fp32 kernels")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--dit-precision", choices=["bf16", "mxfp8"], default="bf16",
                     help="DiT block linears: bf16 (default) or the opt-in MX-fp8 GEMMs (lower precision, faster)")
@@ -195,7 +208,7 @@ def main(argv=None):
                           resample_round=a.resample_round, static=a.static == "True", prompt=a.prompt, negative_prompt=a.negative_prompt,
                           embeds=a.embeds, use_pca_channel_selection=a.use_pca_channel_selection, soften_mask=a.soften_mask,
                           transition_distance=a.transition_distance, decay_type=a.decay_type, save_png=a.save_png, device=a.device,
-                          dit_precision=a.dit_precision, text_encoder=a.text_encoder)
+                          dit_precision=a.dit_precision, text_encoder=a.text_encoder, image_encoder=a.image_encoder)
     print(f"{len(frames)} frames -> {png_dir}")
 
 
