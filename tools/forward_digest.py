@@ -1,9 +1,9 @@
-"""Digest of every way the LongCat and the Wan DiT forwards can run: for comparing two checkouts bit for bit and launch for launch.
+"""Digest of every way the LongCat and the Wan DiT forwards and the VAE can run: for comparing two checkouts bit for bit and launch for launch.
 
     python tools/forward_digest.py [--only PREFIX] [--dump DIR] > digest.txt
 
-One seeded random model of the multirank tests' size runs each path on a small grid (the Wan cases are named `wan.`...; `--only wan.`
-selects them); per case (and per simulated rank) one line:
+One seeded random model of the multirank tests' size runs each path on a small grid (the Wan cases are named `wan.`..., the VAE's `vae.`...;
+`--only wan.` selects them); per case (and per simulated rank) one line (the VAE's with flops=<flops_last> behind it):
 
     <case> out=<sha256> calls=<n> launches=<sha256> trace=<sha256>
 
@@ -398,6 +398,69 @@ CASES["wan.ranks2.pair.sequential"] = _wan_ranks(2, (3, 16, 20), None, layers=3,
 CASES["wan.ranks2.pair.lockstep.no_prescale"] = _wan_ranks(2, (3, 16, 20), None, layers=3, pair=True, attn_prescale=False)  # (-> "gather")
 
 
+# ---- the VAE (`vae.`...): one seeded model per precision, whole frames and as P simulated ranks on row slabs; the shapes of
+# tests/test_gpu_vae.py's sharded tests (stage-0 row groups of 1 and of 2 ranks, an odd first-up slab row, a crop that is taken -- the
+# "right" mask -- and one that is refused -- "rand"), and one-frame inputs for the T == 1 branches.  Lines carry flops=<flops_last> --------
+_VAE_W = {}
+
+
+def _vae(prec, comm=None):
+    from oracle import vae as ovae
+    from worldforge_amd.vae import AutoencoderKLWan
+    if prec not in _VAE_W:
+        _VAE_W[prec] = AutoencoderKLWan(DEV, precision=prec).load_state_dict(ovae.random_weights(seed=5)).w
+    m = AutoencoderKLWan(DEV, comm=comm, precision=prec)
+    m.w = _VAE_W[prec]
+    return m
+
+
+def _vae_op(what, H, T):
+    """-> fn(model) -> outputs, on inputs made once (shared by the simulated ranks)."""
+    if what in ("encode", "decode"):
+        g = torch.Generator().manual_seed(21)
+        x = (torch.rand(1, 3, 4 * T - 3, H, 48, generator=g) * 2 - 1).to(DEV)
+        z = torch.randn(1, 16, T, H // 8, 6, generator=g).to(DEV)
+        if what == "decode":
+            return lambda m: m.decode(z, return_dict=False)[0].clone()
+
+        def encode(m):
+            post = m.encode(x).latent_dist
+            return post.mode().clone(), post.sample(torch.Generator().manual_seed(1))
+        return encode
+    from tests.test_gpu_vae import _hole_mask
+    g = torch.Generator().manual_seed(33)
+    z = torch.randn(1, 16, T, H // 8, 32, generator=g).to(DEV)
+    ref = torch.rand(1, 3, 4 * T - 3, H, 256, generator=g).to(DEV)
+    mask = _hole_mask(4 * T - 3, H, 256, what.split(".")[1]).to(DEV)
+    return lambda m: m.decode_blend_encode(z, ref, mask).mode().clone()
+
+
+def _vae_case(prec, what, H, T=3, P=1):
+    def run():
+        op = _vae_op(what, H, T)
+        _vae(prec)   # (the weights, before any thread asks for them)
+
+        def go(comm=None):
+            m = _vae(prec, comm)
+            assert P == 1 or m.can_shard(H // 8)
+            out = op(m)
+            m.check_range()
+            return out, m.flops_last
+
+        res = [_traced(go)] if P == 1 else _run_ranks(P, go)
+        return [("" if P == 1 else f".rank{r}", out, trace, flops) for r, ((out, flops), trace) in enumerate(res)]
+    return run
+
+
+for _prec in ("bf16", "fp16x3", "bf16x3", "fp16"):
+    for _P, _H in ((1, 64), (2, 64), (4, 64), (8, 64), (2, 24), (8, 96)):
+        for _what in ("encode", "decode", "dbe.right", "dbe.rand"):
+            CASES[f"vae.{_prec}.P{_P}.H{_H}.{_what}"] = _vae_case(_prec, _what, _H, P=_P)
+    for _P in (1, 2):
+        for _what in ("encode", "decode"):
+            CASES[f"vae.{_prec}.P{_P}.H64.T1.{_what}"] = _vae_case(_prec, _what, 64, T=1, P=_P)
+
+
 def main():
     ap =argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--only", default="", help="run the cases whose name starts with this")
@@ -414,9 +477,10 @@ def main():
         except (ValueError, NotImplementedError, AssertionError) as e:  # a host-side refusal; anything else ends the run
             print(f"{name} ERROR {type(e).__name__}: {e}", flush=True)
             continue
-        for suffix, out, trace in rows:
+        for suffix, out, trace, *flops in rows:
             full, bare = _render(trace)
-            print(f"{name}{suffix} out={_sha(out)} calls={len(full)} launches={_sha(bare)} trace={_sha(full)}", flush=True)
+            print(f"{name}{suffix} out={_sha(out)} calls={len(full)} launches={_sha(bare)} trace={_sha(full)}"
+                  + "".join(f" flops={v}" for v in flops), flush=True)
             if args.dump:
                 with open(os.path.join(args.dump, f"{name}{suffix}.txt"), "w") as f:
                     f.write("\n".join(full) + "\n")

@@ -45,7 +45,7 @@ import os
 
 import math
 from types import SimpleNamespace
-from typing import Dict, List, Tuple
+from typing import Dict
 
 import torch
 
@@ -53,123 +53,9 @@ from . import ops
 from . import _ffi
 from ._ffi import WF_BF16, WF_F32, call
 from .dit import EPI_BF16, EPI_F32, EPI_F32_ACC, gemm
-
-DIM, Z_DIM = 96, 16
-DIM_MULT = [1, 2, 4, 4]
-NUM_RES = 2
-T_DOWN = [False, True, True]
-LATENTS_MEAN = [-0.7571, -0.7089, -0.9113, 0.1075, -0.1745, 0.9653, -0.1517, 1.5508, 0.4134, -0.0715, 0.5517, -0.3632,
-                -0.1922, -0.9497, 0.2503, -0.2921]  # vae.py:629-632
-LATENTS_STD = [2.8184, 1.4541, 2.3275, 2.6558, 1.2196, 1.7708, 2.6052, 2.0743, 3.2687, 2.1526, 2.8652, 1.5579, 1.6382,
-               1.1253, 2.8251, 1.9160]  # vae.py:633-636
-
-BF, F32 = torch.bfloat16, torch.float32
-
-
-def encoder_plan() -> List[Tuple]:
-    """vae.py:283-316."""
-    dims = [DIM * u for u in [1] + DIM_MULT]
-    plan = [("conv_in", "encoder.conv1", 3, dims[0])]
-    idx = 0
-    for i, (cin, cout) in enumerate(zip(dims[:-1], dims[1:])):
-        for _ in range(NUM_RES):
-            plan.append(("res", f"encoder.downsamples.{idx}", cin, cout))
-            idx += 1
-            cin = cout
-        if i != len(DIM_MULT) - 1:
-            plan.append(("down3d" if T_DOWN[i] else "down2d", f"encoder.downsamples.{idx}", cout, cout))
-            idx += 1
-    c = dims[-1]
-    plan += [("res", "encoder.middle.0", c, c), ("attn", "encoder.middle.1", c, c), ("res", "encoder.middle.2", c, c),
-             ("head", "encoder.head", c, 2 * Z_DIM)]
-    return plan
-
-
-def decoder_plan() -> List[Tuple]:
-    """vae.py:387-421."""
-    dims = [DIM * u for u in [DIM_MULT[-1]] + DIM_MULT[::-1]]
-    t_up = T_DOWN[::-1]
-    plan = [("conv_in", "decoder.conv1", Z_DIM, dims[0]), ("res", "decoder.middle.0", dims[0], dims[0]),
-            ("attn", "decoder.middle.1", dims[0], dims[0]), ("res", "decoder.middle.2", dims[0], dims[0])]
-    idx = 0
-    for i, (cin, cout) in enumerate(zip(dims[:-1], dims[1:])):
-        if i in (1, 2, 3):
-            cin = cin // 2
-        for _ in range(NUM_RES + 1):
-            plan.append(("res", f"decoder.upsamples.{idx}", cin, cout))
-            idx += 1
-            cin = cout
-        if i != len(DIM_MULT) - 1:
-            plan.append(("up3d" if t_up[i] else "up2d", f"decoder.upsamples.{idx}", cout, cout // 2))
-            idx += 1
-    plan.append(("head", "decoder.head", dims[-1], 3))
-    return plan
-
-
-def diffusers_key_map() -> Dict[str, str]:
-    """diffusers `AutoencoderKLWan` module name -> in-tree twin (`WanVAE_`) module name, for the Wan 2.1 configuration
-    (is_residual=False).  The diffusers class is what the reference executes (INFER:185-189 `AutoencoderKLWan.from_pretrained`; a
-    vendored copy is longcat_video/modules/autoencoder_kl_wan.py: encoder :505-584, decoder :783-872, mid block :430-451, up block
-    :714-753, residual block :311-340, top level :1029-1052).  Leaves (.weight / .bias / .gamma) are appended by the caller."""
-    m = {"encoder.conv_in": "encoder.conv1", "encoder.norm_out": "encoder.head.0", "encoder.conv_out": "encoder.head.2",
-         "decoder.conv_in": "decoder.conv1", "decoder.norm_out": "decoder.head.0", "decoder.conv_out": "decoder.head.2",
-         "quant_conv": "conv1", "post_quant_conv": "conv2"}
-    res = {"norm1": "residual.0", "conv1": "residual.2", "norm2": "residual.3", "conv2": "residual.6", "conv_shortcut": "shortcut"}
-    for side in ("encoder", "decoder"):
-        for j, name in ((0, "resnets.0"), (1, "attentions.0"), (2, "resnets.1")):
-            d, t = f"{side}.mid_block.{name}", f"{side}.middle.{j}"
-            if j == 1:
-                for leaf in ("norm", "to_qkv", "proj"):
-                    m[f"{d}.{leaf}"] = f"{t}.{leaf}"
-            else:
-                for a, b in res.items():
-                    m[f"{d}.{a}"] = f"{t}.{b}"
-    # encoder: down_blocks is the same flat list as the twin's downsamples
-    for kind, p, cin, cout in encoder_plan():
-        if not p.startswith("encoder.downsamples."):
-            continue
-        d = p.replace("encoder.downsamples.", "encoder.down_blocks.")
-        if kind == "res":
-            for a, b in res.items():
-                if a != "conv_shortcut" or cin != cout:
-                    m[f"{d}.{a}"] = f"{p}.{b}"
-        else:
-            m[f"{d}.resample.1"] = f"{p}.resample.1"
-            if kind.endswith("3d"):
-                m[f"{d}.time_conv"] = f"{p}.time_conv"
-    # decoder: up_blocks[i] = {resnets[0..2], upsamplers[0]} against the twin's flat upsamples list
-    blk, j = 0, 0
-    for kind, p, cin, cout in decoder_plan():
-        if not p.startswith("decoder.upsamples."):
-            continue
-        if kind == "res":
-            d = f"decoder.up_blocks.{blk}.resnets.{j}"
-            for a, b in res.items():
-                if a != "conv_shortcut" or cin != cout:
-                    m[f"{d}.{a}"] = f"{p}.{b}"
-            j += 1
-            if j == NUM_RES + 1 and blk == len(DIM_MULT) - 1:
-                blk, j = blk + 1, 0
-        else:
-            d = f"decoder.up_blocks.{blk}.upsamplers.0"
-            m[f"{d}.resample.1"] = f"{p}.resample.1"
-            if kind.endswith("3d"):
-                m[f"{d}.time_conv"] = f"{p}.time_conv"
-            blk, j = blk + 1, 0
-    return m
-
-
-def diffusers_to_twin_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """Rename a diffusers-layout AutoencoderKLWan state dict to the twin's names (tensors are shared, shapes are the same up to the
-    trailing singleton dims of the RMS-norm gammas, which the loader flattens).  Unknown or missing parameters raise KeyError."""
-    km = diffusers_key_map()
-    out = {}
-    for k, v in sd.items():
-        base, _, leaf = k.rpartition(".")
-        if base not in km:
-            raise KeyError(f"unmapped diffusers AutoencoderKLWan parameter {k!r}")
-        out[f"{km[base]}.{leaf}"] = v
-    return out
+# (the plans, the constants, the key map and weight_operand are imported from this module by the entry points, the tools and the tests)
+from .vae_weights import (BF, F32, LATENTS_MEAN, LATENTS_STD, T_DOWN, Z_DIM, decoder_plan, diffusers_key_map,  # noqa: F401
+                          diffusers_to_twin_state_dict, encoder_plan, first_up, pack_state_dict, random_state_dict, weight_operand)
 
 
 class _LatentDist:
@@ -190,34 +76,6 @@ class _LatentDist:
         else:
             noise = torch.randn(self._mean.shape, generator=generator, dtype=self._mean.dtype, device=self._mean.device)
         return self._mean + std * noise
-
-
-def weight_operand(w: torch.Tensor, precision: str, device):
-    """f32 [..., Cin] weight (host) -> (the matrix-core weight operand of `precision` on `device`, acc_scale or None).  acc_scale (fp16
-    operand modes only; None = 1): the operand is stored times 2^k and the kernels multiply their accumulators by 2^-k."""
-    w = w.to(F32)
-    if precision not in ("bf16x3", "fp16x3", "fp16"):
-        return w.to(device=device, dtype=BF).contiguous(), None
-    op = torch.float16 if precision in ("fp16x3", "fp16") else BF
-    scale = None
-    if op == torch.float16:
-        # hi = fp16(w), lo = fp16(w - hi): lo is an fp16 SUBNORMAL (absolute floor 2^-25) for |w| < 2^-3 -- VAE weights are ~0.02, so the
-        # split carried them to ~2^-18 relative, not the 2^-22 of its normal range (VERDICT r4 weak #5).  Store the matrix times an exact
-        # power of two that puts its largest magnitude into [2^13, 2^14) (every weight above 2^-17 of it then has a normal lo; fp16 tops
-        # out at 2^16) and hand the kernels acc_scale = 2^-k: out = acc * 2^-k + bias, exact.
-        mx = float(w.abs().max())
-        if not math.isfinite(mx):
-            raise ValueError("a VAE weight is not finite")
-        if mx > 0.0:
-            k = 13 - math.floor(math.log2(mx))
-            k = max(-126, min(126, k))
-            w = w * (2.0 ** k)
-            scale = 2.0 ** -k
-    hi = w.to(op)
-    if precision == "fp16":   # the one-term operand (the scaled weight can no longer leave the fp16 range)
-        return hi.to(device).contiguous(), scale
-    lo = (w - hi.to(F32)).to(op)
-    return torch.cat([hi, hi, lo], dim=-1).to(device).contiguous(), scale  # weight side of wf_split_bf16x3 / wf_split_f16x3
 
 
 class AutoencoderKLWan:
@@ -255,7 +113,6 @@ class AutoencoderKLWan:
         self._sfx = "_f16" if self.f16 else ""         # the C-ABI entry points of that element type
         self.device = torch.device(device)
         self.comm = comm  # row-slab sharding of the high-resolution stages over the ranks of `comm` (parallel.Comm or a stand-in)
-        self._reps = 1    # ranks per row group while a sharded stage runs (see _row_groups)
         self.config = SimpleNamespace(z_dim=Z_DIM, latents_mean=LATENTS_MEAN, latents_std=LATENTS_STD)
         self.temperal_downsample = list(T_DOWN)
         self.w: Dict[str, torch.Tensor] = {}
@@ -265,106 +122,7 @@ class AutoencoderKLWan:
     # weights (keys as in WanVAE_.state_dict())
     # ------------------------------------------------------------------------------------------------------------
     def load_state_dict(self, sd: Dict[str, torch.Tensor]):
-        dev = self.device
-        W: Dict[str, torch.Tensor] = {}
-
-        # W[key + ".scale"] (a Python float, fp16 operand modes only; absent = 1): acc_scale = 2^-k of a weight operand stored scaled by 2^k -- kept
-        # in the weight dict so that instances sharing `w` share it
-
-        def operand(w, key):  # f32 [..., Cin] (host) -> the matrix-core weight operand on the device
-            out, scale = weight_operand(w, self.precision, dev)
-            if scale is not None:
-                W[key + ".scale"] = scale
-            return out
-
-        def mfma_conv(p):  # [Cout,Cin,kt,kh,kw] -> bf16 [Cout, taps, Cin]
-            w = sd[p + ".weight"]
-            if w.dim() == 4:
-                w = w.unsqueeze(2)
-            co, ci = w.shape[:2]
-            W[p + ".w"] = operand(w.permute(0, 2, 3, 4, 1).reshape(co, -1, ci), p + ".w")
-            W[p + ".b"] = sd[p + ".bias"].to(device=dev, dtype=F32).contiguous()
-
-        def mfma_conv_padded(p, cin_pad=None, cout_pad=None):
-            """Thin layers on the MFMA path: zero-pad Cin to a 32-channel K slice / Cout to a multiple of 4 (the kernel
-            computes a 96-wide tile anyway and only stores Cout columns)."""
-            w = sd[p + ".weight"].to(F32)
-            b = sd[p + ".bias"].to(F32)
-            co, ci = w.shape[:2]
-            cip, cop = cin_pad or ci, cout_pad or co
-            wp = torch.zeros((cop, cip) + tuple(w.shape[2:]), dtype=F32)
-            wp[:co, :ci] = w
-            bp = torch.zeros(cop, dtype=F32)
-            bp[:co] = b
-            W[p + ".w"] = operand(wp.permute(0, 2, 3, 4, 1).reshape(cop, -1, cip), p + ".w")
-            W[p + ".b"] = bp.to(dev)
-
-        def small_conv(p, cout_pad=None):  # -> f32 [taps, Cin, Cout]
-            w = sd[p + ".weight"].to(F32)
-            b = sd[p + ".bias"].to(F32)
-            co, ci = w.shape[:2]
-            cop = cout_pad or co
-            wp = torch.zeros((cop, ci) + tuple(w.shape[2:]), dtype=F32)
-            wp[:co] = w
-            bp = torch.zeros(cop, dtype=F32)
-            bp[:co] = b
-            W[p + ".w"] = wp.permute(2, 3, 4, 1, 0).reshape(-1, ci, cop).to(dev).contiguous()
-            W[p + ".b"] = bp.to(dev)
-
-        def lin(p):  # 1x1(x1) conv as GEMM weight bf16 [Cout, Cin]
-            w = sd[p + ".weight"]
-            W[p + ".w"] = operand(w.reshape(w.shape[0], w.shape[1]), p + ".w")
-            W[p + ".b"] = sd[p + ".bias"].to(device=dev, dtype=F32).contiguous()
-
-        def gamma(p):
-            W[p] = sd[p].reshape(-1).to(device=dev, dtype=F32).contiguous()
-
-        def up_phases(p):
-            """Nearest-2x upsample + 3 x 3 conv (vae.py:76-86) as four 2 x 2 convolutions on the source grid: output (2y + py, 2x + px) reads
-            source rows {y - 1 + py, y + py}; the 3 x 3 taps landing on the same source pixel are summed here, in fp32, before the operand
-            split -- 4 / 9 of the multiply-adds, same result up to fp32 re-association."""
-            w = sd[p + ".weight"].to(F32)
-            if w.dim() == 5:
-                w = w[:, :, 0]
-            groups = (([0], [1, 2]), ([0, 1], [2]))  # [phase][source offset] -> the 3-tap indices that read it
-            for py in range(2):
-                for px in range(2):
-                    wp = torch.stack([torch.stack([sum(w[:, :, dy, dx] for dy in groups[py][a] for dx in groups[px][b]) for b in range(2)], dim=-1)
-                                      for a in range(2)], dim=-2)  # [Cout, Cin, 2, 2]
-                    W[f"{p}.ph{py}{px}.w"] = operand(wp.permute(0, 2, 3, 1).reshape(wp.shape[0], 4, wp.shape[1]), f"{p}.ph{py}{px}.w")
-
-        first_up = True
-        for plan in (encoder_plan(), decoder_plan()):
-            for kind, p, cin, cout in plan:
-                if kind == "conv_in":
-                    mfma_conv_padded(p, cin_pad=32)
-                elif kind == "res":
-                    gamma(p + ".residual.0.gamma")
-                    mfma_conv(p + ".residual.2")
-                    gamma(p + ".residual.3.gamma")
-                    mfma_conv(p + ".residual.6")
-                    if cin != cout:
-                        lin(p + ".shortcut")
-                elif kind == "attn":
-                    gamma(p + ".norm.gamma")
-                    lin(p + ".to_qkv")
-                    lin(p + ".proj")
-                elif kind in ("down2d", "down3d", "up2d", "up3d"):
-                    mfma_conv(p + ".resample.1")
-                    if kind.startswith("up"):
-                        # every upsampling conv but the first (small, and its row slabs of the sharded decoder may start on an odd row) runs
-                        # as four phase convolutions
-                        if not first_up:
-                            up_phases(p + ".resample.1")
-                        first_up = False
-                    if kind.endswith("3d"):
-                        mfma_conv(p + ".time_conv")
-                elif kind == "head":
-                    gamma(p + ".0.gamma")
-                    mfma_conv_padded(p + ".2", cout_pad=(cout + 31) // 32 * 32)  # one 32-channel output block of the 3x3x3 kernel
-        small_conv("conv1")
-        small_conv("conv2", cout_pad=32)  # decoder input, zero-padded to one 32-channel MFMA K slice
-        self.w = W
+        self.w = pack_state_dict(sd, self.precision, self.device)
         return self
 
     def load_diffusers_state_dict(self, sd: Dict[str, torch.Tensor]):
@@ -382,42 +140,7 @@ class AutoencoderKLWan:
 
     def init_random(self, seed: int = 0):
         """Synthetic weights of the real shapes, generated on the host in twin layout (127 M parameters)."""
-        g = torch.Generator().manual_seed(seed)
-        sd = {}
-
-        def conv(p, cin, cout, k):
-            sd[p + ".weight"] = torch.randn((cout, cin) + k, generator=g) / math.sqrt(cin * math.prod(k))
-            sd[p + ".bias"] = 0.02 * torch.randn(cout, generator=g)
-
-        for plan in (encoder_plan(), decoder_plan()):
-            for kind, p, cin, cout in plan:
-                if kind == "conv_in":
-                    conv(p, cin, cout, (3, 3, 3))
-                elif kind == "res":
-                    sd[p + ".residual.0.gamma"] = 1 + 0.05 * torch.randn(cin, generator=g)
-                    conv(p + ".residual.2", cin, cout, (3, 3, 3))
-                    sd[p + ".residual.3.gamma"] = 1 + 0.05 * torch.randn(cout, generator=g)
-                    conv(p + ".residual.6", cout, cout, (3, 3, 3))
-                    if cin != cout:
-                        conv(p + ".shortcut", cin, cout, (1, 1, 1))
-                elif kind == "attn":
-                    sd[p + ".norm.gamma"] = 1 + 0.05 * torch.randn(cin, generator=g)
-                    conv(p + ".to_qkv", cin, 3 * cin, (1, 1))
-                    conv(p + ".proj", cin, cin, (1, 1))
-                elif kind in ("down2d", "down3d"):
-                    conv(p + ".resample.1", cin, cin, (3, 3))
-                    if kind == "down3d":
-                        conv(p + ".time_conv", cin, cin, (3, 1, 1))
-                elif kind in ("up2d", "up3d"):
-                    conv(p + ".resample.1", cin, cin // 2, (3, 3))
-                    if kind == "up3d":
-                        conv(p + ".time_conv", cin, cin * 2, (3, 1, 1))
-                elif kind == "head":
-                    sd[p + ".0.gamma"] = 1 + 0.05 * torch.randn(cin, generator=g)
-                    conv(p + ".2", cin, cout, (3, 3, 3))
-        conv("conv1", 2 * Z_DIM, 2 * Z_DIM, (1, 1, 1))
-        conv("conv2", Z_DIM, Z_DIM, (1, 1, 1))
-        return self.load_state_dict(sd)
+        return self.load_state_dict(random_state_dict(seed))
 
     # ------------------------------------------------------------------------------------------------------------
     # kernels wrappers; activations are channels-last [T, H, W, C]
@@ -598,14 +321,14 @@ class AutoencoderKLWan:
             raise RuntimeError(f"AutoencoderKLWan.{what}: an activation left the fp16 range (|x| > 65504) or was NaN under precision="
                                f"{self.precision!r}; use precision='bf16x3' (8-bit exponent) for these weights / inputs")
 
-    def _res(self, x, p, cin, cout):
-        """vae.py:186-220."""
+    def _res(self, x, p, cin, cout, k=None):
+        """vae.py:186-220.  k: see _run."""
         T, H, Wd, _ = x.shape
         W = self.w
-        a = self._rms(x, W[p + ".residual.0.gamma"], blocked=True)
-        y, _ = self._conv(a, p + ".residual.2", T, H, Wd, cout, (3, 3, 3), pt=2, ps=1)
+        a, ph = self._halo_operand(x, W[p + ".residual.0.gamma"], k)
+        y, _ = self._conv(a, p + ".residual.2", T, H, Wd, cout, (3, 3, 3), pt=2, ps=1, ph=ph)
         del a
-        a2 = self._rms(y, W[p + ".residual.3.gamma"], blocked=True)
+        a2, ph = self._halo_operand(y, W[p + ".residual.3.gamma"], k)
         del y
         if cin != cout:
             xb = self._operand(x)
@@ -615,7 +338,7 @@ class AutoencoderKLWan:
             del xb
         else:
             h = x
-        out, _ = self._conv(a2, p + ".residual.6", T, H, Wd, cout, (3, 3, 3), pt=2, ps=1, resid=h)
+        out, _ = self._conv(a2, p + ".residual.6", T, H, Wd, cout, (3, 3, 3), pt=2, ps=1, ph=ph, resid=h)
         return out
 
     def _attn(self, x, p, rows=None):
@@ -708,15 +431,16 @@ class AutoencoderKLWan:
         self.flops_last += n3 * (T * (4 * nq * hw * C) + 2 * T * hw * C * 3 * C + 2 * T * nq * C * C)
         return x
 
-    def _down(self, x, p, C, temporal):
-        """vae.py:87-96, 139-159."""
+    def _down(self, x, p, C, temporal, k=None):
+        """vae.py:87-96, 139-159: ZeroPad2d((0,1,0,1)) + stride-2 conv (of a row slab's halo rows only the bottom one is read), then the
+        stride-2 temporal conv.  k: see _run."""
         T, H, Wd, _ = x.shape
         Ho, Wo = H // 2, Wd // 2
-        xb = self._operand(x)
+        xb, ph = self._halo_pad_of(x, k)
         if not temporal or T == 1:
-            y, _ = self._conv(xb, p + ".resample.1", T, Ho, Wo, C, (1, 3, 3), ss=2, ps=0)
+            y, _ = self._conv(xb, p + ".resample.1", T, Ho, Wo, C, (1, 3, 3), ss=2, ps=0, ph=ph)
             return y
-        y, yb = self._conv(xb, p + ".resample.1", T, Ho, Wo, C, (1, 3, 3), ss=2, ps=0, out_f32=True, out_bf16=not self.wide)
+        y, yb = self._conv(xb, p + ".resample.1", T, Ho, Wo, C, (1, 3, 3), ss=2, ps=0, ph=ph, out_f32=True, out_bf16=not self.wide)
         del xb
         if self.wide:
             yb = self._operand(y)
@@ -755,23 +479,27 @@ class AutoencoderKLWan:
         self.flops_last += 4 * 2 * T * n_rows * Wd * Cout * 4 * Cin
         return out
 
-    def _run(self, x, plan):
+    def _run(self, x, plan, k=None, g=0):
+        """The layers of `plan` on x.  k = None: x holds whole frames.  k >= 1: x is the row slab of row group g, whose k consecutive ranks
+        hold the same rows (_row_groups; k = 1: every rank its own slab): a conv operand's top and bottom rows then come from the
+        neighbouring groups instead of the kernel's zero padding (_halo_operand, _halo_pad_of), and the attention's keys / values are
+        the gathered frame (_attn_group).  Per output element the same arithmetic either way."""
         W = self.w
         for kind, p, cin, cout in plan:
             T, H, Wd, _ = x.shape
-            if kind == "conv_in":  # x arrives bf16, zero-padded to 32 channels
+            if kind == "conv_in":  # x arrives bf16, zero-padded to 32 channels (a slab's first conv is its caller's: its halo is cut, not exchanged)
                 x, _ = self._conv(x, p, T, H, Wd, cout, (3, 3, 3), pt=2, ps=1)
             elif kind == "res":
-                x = self._res(x, p, cin, cout)
+                x = self._res(x, p, cin, cout, k)
             elif kind == "attn":
-                x = self._attn(x, p)
+                x = self._attn(x, p) if k is None else self._attn_group(x, p, g, k)
             elif kind in ("down2d", "down3d"):
-                x = self._down(x, p, cin, kind == "down3d")
-            elif kind in ("up2d", "up3d"):
+                x = self._down(x, p, cin, kind == "down3d", k)
+            elif kind in ("up2d", "up3d"):  # (whole frames: a slab's source rows are its caller's, _up_slab)
                 x = self._up(x, p, cin, kind == "up3d")
             elif kind == "head":
-                a = self._rms(x, W[p + ".0.gamma"], blocked=True)
-                x, _ = self._conv(a, p + ".2", T, H, Wd, (cout + 31) // 32 * 32, (3, 3, 3), pt=2, ps=1)
+                a, ph = self._halo_operand(x, W[p + ".0.gamma"], k)
+                x, _ = self._conv(a, p + ".2", T, H, Wd, (cout + 31) // 32 * 32, (3, 3, 3), pt=2, ps=1, ph=ph)
         return x
 
     # ------------------------------------------------------------------------------------------------------------
@@ -781,79 +509,59 @@ class AutoencoderKLWan:
     # all-gather their top / bottom rows of the convolution INPUT (bf16) and pick their neighbours' (zeros at the image edge).
     # Only all-gather is used.  Results are bit-identical to the unsharded path (same per-pixel accumulation order).
     # ------------------------------------------------------------------------------------------------------------
-    def _halo_pad(self, a):
+    def _halo_fill(self, out, up, down):
+        """out [T,Hs+2,...] whose rows 1 .. Hs are this rank's: rows 0 and Hs+1 <- the neighbours' boundary rows `up` and `down` (None at the
+        image edge: zeros), as the exchange handed them over.  Round 5: exchanged with the two neighbours only (parallel.Comm.neighbor_rows:
+        all-gathers inside two-rank groups), not all-gathered over the whole job -- a rank receives the 2 rows it needs instead of 2 (P - 1)."""
+        for row, src in ((0, up), (out.shape[1] - 1, down)):
+            if src is not None:
+                out[:, row].copy_(src)
+            else:
+                out[:, row].zero_()
+        return out
+
+    def _halo_pad(self, a, k):
         """a [T,Hs,W,C] (or slice-major [T,Hs,S,W,16]) bf16 -> [T,Hs+2,...] with the neighbours' boundary rows (zeros at the image
         boundary)."""
         T, Hs = a.shape[:2]
         out = torch.empty((T, Hs + 2) + tuple(a.shape[2:]), dtype=a.dtype, device=a.device)
         out[:, 1:Hs + 1].copy_(a)
-        return self._halo_fill(out)
+        return self._halo_fill(out, *self.comm.neighbor_rows(out[:, 1], out[:, Hs], k))
 
-    def _halo_pad_of(self, x):
-        """The conv operand of the row slab x f32 [T,Hs,W,C], halo-padded: [T,Hs+2,W,..] with the neighbours' boundary rows (zeros at the image
-        edge).  The two border rows are produced FIRST: their operand rows travel to the neighbours on the communication stream
-        (Comm.neighbor_rows_async) while the whole slab's operand is produced -- straight into rows 1 .. Hs of the padded buffer
-        (wf_operand_rows: round 5 produced the slab's operand and copied it in, 1-2 GB per full-resolution layer).  Per pixel the same
-        arithmetic wherever the pixel sits: bit-identical to exchanging rows of the produced slab."""
+    def _halo_pad_of(self, x, k):
+        """The plain conv operand of the f32 stream x and the top padding `ph` its stride-2 conv (ps = 0) is told.  k = None (whole
+        frames): _operand(x), the kernel pads.  k >= 1: x is a row slab [T,Hs,W,C] (k: see _run) -> [T,Hs+2,W,..] with the neighbours'
+        boundary rows (zeros at the image edge), ph = -1: the top halo row is skipped.  The two border rows are produced FIRST: their operand
+        rows travel to the neighbours on the communication stream (Comm.neighbor_rows_async) while the whole slab's operand is produced --
+        straight into rows 1 .. Hs of the padded buffer (wf_operand_rows: round 5 produced the slab's operand and copied it in, 1-2 GB per
+        full-resolution layer).  Per pixel the same arithmetic wherever the pixel sits: bit-identical to exchanging rows of the produced
+        slab."""
+        if k is None:
+            return self._operand(x), None
         T, Hs, Wd, C = x.shape
         e_op = self._operand(torch.stack([x[:, 0], x[:, Hs - 1]], dim=1))
-        pending = self.comm.neighbor_rows_async(e_op[:, 0], e_op[:, 1], self._reps)
+        pending = self.comm.neighbor_rows_async(e_op[:, 0], e_op[:, 1], k)
         nC = self.terms * C
         out = torch.empty((T, Hs + 2, Wd, nC), dtype=self.OP, device=x.device)
         fmt = (1 if self.f16 else 0) if self.x3 else (2 if self.f16 else 3)
         call("wf_operand_rows", x.data_ptr(), C, out.data_ptr(), nC, T * Hs * Wd, C, fmt, 0, Hs * Wd, 2 * Wd, Wd, ops.stream())
-        up, down = pending()
-        if up is not None:
-            out[:, 0].copy_(up)
-        else:
-            out[:, 0].zero_()
-        if down is not None:
-            out[:, Hs + 1].copy_(down)
-        else:
-            out[:, Hs + 1].zero_()
-        return out
+        return self._halo_fill(out, *pending()), -1
 
-    def _halo_fill(self, out):
-        """out [T,Hs+2,...] whose rows 1 .. Hs are this rank's: rows 0 and Hs+1 <- the neighbours' boundary rows (zeros at the image edge).
-        Round 5: exchanged with the two neighbours only (parallel.Comm.neighbor_rows: all-gathers inside two-rank groups), not all-gathered
-        over the whole job -- a rank receives the 2 rows it needs instead of 2 (P - 1)."""
-        comm = self.comm
-        T, Hs = out.shape[0], out.shape[1] - 2
-        a = out[:, 1:Hs + 1]
-        reps = self._reps  # ranks per row group (1: every rank its own slab; > 1: `reps` consecutive ranks hold the same slab)
-        up, down = comm.neighbor_rows(a[:, 0], a[:, Hs - 1], reps)
-        if up is not None:
-            out[:, 0].copy_(up)
-        else:
-            out[:, 0].zero_()
-        if down is not None:
-            out[:, Hs + 1].copy_(down)
-        else:
-            out[:, Hs + 1].zero_()
-        return out
-
-    def _halo_operand(self, x, gamma):
-        """RMS_norm + SiLU of a row slab as the halo-padded conv operand: the norm kernel writes the slab's own rows in place (no copy)."""
-        C = x.shape[-1]
-        if C % 32 == 0:
+    def _halo_operand(self, x, gamma, k):
+        """RMS_norm + SiLU of the f32 stream x as the operand of a 3x3x3 conv (ps = 1), and the top padding `ph` that conv is told.  k = None
+        (whole frames): _rms(blocked=True), the kernel pads.  k >= 1: x is a row slab (k: see _run) -> the halo-padded operand, ph = 0;
+        the norm kernel writes the slab's own rows in place (no copy)."""
+        if k is None:
+            return self._rms(x, gamma, blocked=True), None
+        if x.shape[-1] % 32 == 0:
             # the two border rows first: their operand rows travel to the neighbours on the communication stream while the norm kernel
             # produces the whole slab (per pixel the same arithmetic wherever the pixel sits: bit-identical to exchanging rows of the slab)
             T, Hs = x.shape[:2]
             edge = torch.stack([x[:, 0], x[:, Hs - 1]], dim=1)                       # [T, 2, W, C] f32
             e_op = self._rms(edge, gamma, blocked=True)                              # [T, 2, S, W, 16]
-            pending = self.comm.neighbor_rows_async(e_op[:, 0], e_op[:, 1], self._reps)
-            out = self._rms(x, gamma, blocked=True, halo=True)
-            up, down = pending()
-            if up is not None:
-                out[:, 0].copy_(up)
-            else:
-                out[:, 0].zero_()
-            if down is not None:
-                out[:, Hs + 1].copy_(down)
-            else:
-                out[:, Hs + 1].zero_()
-            return out
-        return self._halo_pad(self._rms(x, gamma, blocked=True))
+            pending = self.comm.neighbor_rows_async(e_op[:, 0], e_op[:, 1], k)
+            return self._halo_fill(self._rms(x, gamma, blocked=True, halo=True), *pending()), 0
+        return self._halo_pad(self._rms(x, gamma, blocked=True), k), 0
 
     def _rows_from_full(self, x, r0, r1):
         """Rows [r0, r1) of a replicated [T,H,W,C] tensor with zero rows outside the image -> contiguous slab."""
@@ -863,25 +571,25 @@ class AutoencoderKLWan:
         out[:, lo - r0:hi - r0].copy_(x[:, lo:hi])
         return out
 
-    def _gather_rows(self, slab):
-        """[T,Hs,W,C] per rank -> full [T,P*Hs,W,C] on every rank."""
+    def _gather_rows(self, slab, k=1):
+        """[T,Hs,W,C] per rank (k consecutive ranks hold the same slab) -> full [T,(P/k)*Hs,W,C] on every rank."""
         comm = self.comm
         allr = torch.empty((comm.world,) + tuple(slab.shape), dtype=slab.dtype, device=slab.device)
         comm.all_gather(allr, slab.contiguous())
-        if self._reps > 1:  # one copy per row group
-            allr = allr[::self._reps]
+        if k > 1:  # one copy per row group
+            allr = allr[::k]
         return allr.permute(1, 0, 2, 3, 4).reshape(slab.shape[0], allr.shape[0] * slab.shape[1], slab.shape[2], slab.shape[3]).contiguous()
 
-    def _attn_group(self, x, p, g: int, Hg: int):
+    def _attn_group(self, x, p, g: int, reps: int):
         """The mid-block attention of row group g (x: the group's slab [T, Hg, W, C], the same on the group's `reps` ranks): keys / values are
         the whole frame (gathered), and the group's QUERY rows are divided among its replicas (round 6: each of the `reps` ranks computed all
         Hg rows before -- at 8 ranks, 4 groups x 2, every rank did a quarter of the queries instead of an eighth); the replicas' rows come back
         by one all-gather.  Per output row the arithmetic of the whole-frame call: bit-identical."""
-        comm, reps = self.comm, self._reps
-        full = self._gather_rows(x)
+        comm = self.comm
+        T, Hg, Wd, C = x.shape
+        full = self._gather_rows(x, reps)
         if reps == 1:
             return self._attn(full, p, rows=(g * Hg, (g + 1) * Hg))
-        T, _, Wd, C = x.shape
         j, per = comm.rank % reps, -(-Hg // reps)
         r0, r1 = min(j * per, Hg), min((j + 1) * per, Hg)
         mine = torch.zeros((T, per, Wd, C), dtype=F32, device=x.device)
@@ -905,24 +613,6 @@ class AutoencoderKLWan:
             if P % G == 0 and h % G == 0 and (not even or (h // G) % 2 == 0):
                 return G
         return 1
-
-    def _res_slab(self, x, p, cin, cout):
-        T, Hs, Wd, _ = x.shape
-        W = self.w
-        a = self._halo_operand(x, W[p + ".residual.0.gamma"])
-        y, _ = self._conv(a, p + ".residual.2", T, Hs, Wd, cout, (3, 3, 3), pt=2, ps=1, ph=0)
-        del a
-        a2 = self._halo_operand(y, W[p + ".residual.3.gamma"])
-        del y
-        if cin != cout:
-            xb = self._operand(x)
-            h = torch.empty((T, Hs, Wd, cout), dtype=F32, device=x.device)
-            self._gemm(xb.view(-1, xb.shape[-1]), W[p + ".shortcut.w"], W[p + ".shortcut.b"], h.view(-1, cout), EPI_F32, wkey=p + ".shortcut.w")
-            del xb
-        else:
-            h = x
-        out, _ = self._conv(a2, p + ".residual.6", T, Hs, Wd, cout, (3, 3, 3), pt=2, ps=1, ph=0, resid=h)
-        return out
 
     def _time_up(self, xb, p, C):
         """'upsample3d' temporal part (pointwise in space) on the conv operand xb of x: [T,..] -> [1+2(T-1),..] as an operand again.
@@ -967,25 +657,6 @@ class AutoencoderKLWan:
         out, _ = self._conv(xsrc_b, p + ".resample.1", T, Ho, 2 * Wd, C // 2, (1, 3, 3), ps=1, ph=1 + 2 * s0 - y0, up2=True)
         return out
 
-    def _down_slab(self, x, p, C, temporal):
-        """fp32 slab [T,Hs,W,C] -> [T',Hs/2,W/2,C]  (ZeroPad2d((0,1,0,1)) + stride-2 conv: bottom halo row only)."""
-        T, Hs, Wd, _ = x.shape
-        xpad = self._halo_pad_of(x)
-        Ho, Wo = Hs // 2, Wd // 2
-        if not temporal or T == 1:
-            y, _ = self._conv(xpad, p + ".resample.1", T, Ho, Wo, C, (1, 3, 3), ss=2, ps=0, ph=-1)
-            return y
-        y, yb = self._conv(xpad, p + ".resample.1", T, Ho, Wo, C, (1, 3, 3), ss=2, ps=0, ph=-1, out_f32=True, out_bf16=not self.wide)
-        if self.wide:
-            yb = self._operand(y)
-        To = (T - 1) // 2
-        out = torch.empty((1 + To, Ho, Wo, C), dtype=F32, device=x.device)
-        out[0].copy_(y[0])
-        W = self.w
-        call("wf_conv3d_cl" + self._sfx, yb.data_ptr(), W[p + ".time_conv.w"].data_ptr(), W[p + ".time_conv.b"].data_ptr(), None,
-             out[1:].data_ptr(), None, T, Ho, Wo, yb.shape[-1], To, Ho, Wo, C, 3, 1, 1, 2, 1, 0, 0, 0, 0, 0, None, *self._acc_scale(p + ".time_conv.w"), ops.stream())
-        return out
-
     def can_shard(self, H_lat: int) -> bool:
         """Row sharding needs every sharded stage to hold an integer (even, where a stride-2 conv follows) number of rows."""
         if self.comm is None or self.comm.world == 1:
@@ -993,38 +664,27 @@ class AutoencoderKLWan:
         P = self.comm.world
         return (2 * H_lat) % P == 0 and (8 * H_lat) % (4 * P) == 0
 
-    def _decode_one_sharded(self, z: torch.Tensor, gather: bool = True, crop=None) -> torch.Tensor:
-        """gather=False: return this rank's row slab [3, F, 8h/P, 8w] (rows rank * 8h/P ...) instead of the gathered video.  crop: the
-        latent columns decoded after the latent-resolution stage (decode(columns=...))."""
+    def _decode_stage0_sharded(self, x, plan):
+        """The latent-resolution stage of the sharded decoder (conv_in, 5 residual blocks, the mid-block attention at h x w) on the replicated
+        operand x -> whole frames on every rank [T,h,w,384] fp32: in G row groups of h / G rows, world / G ranks per group, where h has
+        such a divisor."""
         comm = self.comm
-        P, rank = comm.world, comm.rank
-        C, T, h, w = z.shape
-        x = torch.empty((T, h, w, Z_DIM), dtype=F32, device=self.device)
-        call("wf_ncthw_to_cl", z.data_ptr(), x.data_ptr(), None, Z_DIM, Z_DIM, T * h * w, ops.stream())
-        x = self._latent_in(x, T, h, w)
-        plan = decoder_plan()
-        first_up = next(i for i, e in enumerate(plan) if e[0] in ("up2d", "up3d"))
+        T, h, w, _ = x.shape
         G = self._row_groups(h)
-        if G > 1:
-            # stage 0 (conv_in, 5 residual blocks, the mid-block attention at h x w) in G row groups of h / G rows, world / G ranks per group
-            self._reps = P // G
-            try:
-                g, Hg = rank // self._reps, h // G
-                kind, p, cin, cout = plan[0]
-                x, _ = self._conv(self._rows_from_full(x, g * Hg - 1, (g + 1) * Hg + 1), p, T, Hg, w, cout, (3, 3, 3), pt=2, ps=1, ph=0)
-                for kind, p, cin, cout in plan[1:first_up]:
-                    if kind == "res":
-                        x = self._res_slab(x, p, cin, cout)
-                    else:  # attention: the keys / values are the whole frame, the queries this group's rows
-                        x = self._attn_group(x, p, g, Hg)
-                x = self._gather_rows(x)                       # whole frames on every rank again: [T,h,w,384] fp32
-            finally:
-                self._reps = 1
-        else:
-            x = self._run(x, plan[:first_up])                  # stage 0 replicated: [T,h,w,384] fp32
-        if crop is not None:
-            x = x[:, :, crop[0]:crop[1]].contiguous()
-        kind, p, cin, cout = plan[first_up]
+        if G == 1:
+            return self._run(x, plan)
+        k = comm.world // G
+        g, Hg = comm.rank // k, h // G
+        kind, p, cin, cout = plan[0]
+        x, _ = self._conv(self._rows_from_full(x, g * Hg - 1, (g + 1) * Hg + 1), p, T, Hg, w, cout, (3, 3, 3), pt=2, ps=1, ph=0)
+        return self._gather_rows(self._run(x, plan[1:], k, g), k)
+
+    def _decode_ups_sharded(self, x, plan):
+        """The decoder from its first upsampling layer on (`plan`), sharded: replicated whole frames x [T,h,w,C] f32 -> this rank's rows
+        (rank * 8h/P ...) of the head's output."""
+        P, rank = self.comm.world, self.comm.rank
+        h = x.shape[1]
+        kind, p, cin, cout = plan[0]
         Hs = 2 * h // P                                        # my rows at the next resolution
         y0 = rank * Hs
         s0, s1 = (y0 - 1) >> 1, ((y0 + Hs) >> 1) + 1               # source rows incl. halo (s0 = -1 -> zero row)
@@ -1032,29 +692,15 @@ class AutoencoderKLWan:
         x = self._up_slab(src, p, cin, kind == "up3d", s0, y0, Hs, h)
         h_cur = 2 * h                                          # full image height at the current resolution
         row0 = y0                                              # global first row of my slab at the current resolution
-        for kind, p, cin, cout in plan[first_up + 1:]:
-            if kind == "res":
-                x = self._res_slab(x, p, cin, cout)
-            elif kind in ("up2d", "up3d"):
-                Hcur = x.shape[1]
-                x = self._up_slab(self._halo_pad_of(x), p, cin, kind == "up3d", row0 - 1, 2 * row0, 2 * Hcur, h_cur)
+        ups = [i for i, e in enumerate(plan) if e[0] in ("up2d", "up3d")] + [len(plan)]
+        for a, b in zip(ups, ups[1:]):                         # the layers up to the next upsampling layer, then that layer
+            x = self._run(x, plan[a + 1:b], 1)
+            if b < len(plan):
+                kind, p, cin, cout = plan[b]
+                x = self._up_slab(self._halo_pad_of(x, 1)[0], p, cin, kind == "up3d", row0 - 1, 2 * row0, 2 * x.shape[1], h_cur)
                 row0 *= 2
                 h_cur *= 2
-            elif kind == "head":
-                Tn, Hn, Wn, _ = x.shape
-                a = self._halo_operand(x, self.w[p + ".0.gamma"])
-                x, _ = self._conv(a, p + ".2", Tn, Hn, Wn, (cout + 31) // 32 * 32, (3, 3, 3), pt=2, ps=1, ph=0)
-        # channels-last (32 padded channels) -> [3, F, rows, W] on the SLAB, then -- for the gathered form -- one all-gather of the 3-channel
-        # slabs (round 5 gathered the padded 32-channel slabs, 4.1 GB at C2, and converted the whole video on every rank)
-        x = x.contiguous()
-        Fo, Hs_, Wo, Cy = x.shape
-        out = torch.empty((3, Fo, Hs_, Wo), dtype=F32, device=self.device)
-        call("wf_cl_to_ncthw", x.data_ptr(), out.data_ptr(), 3, Cy, Fo * Hs_ * Wo, 1.0, ops.stream())
-        if gather:
-            allr = torch.empty((P, 3, Fo, Hs_, Wo), dtype=F32, device=self.device)
-            comm.all_gather(allr, out)
-            out = allr.permute(1, 2, 0, 3, 4).reshape(3, Fo, P * Hs_, Wo).contiguous()
-        return out if crop is None else self._uncrop(out, crop, w)
+        return x
 
     def _encode_one_sharded(self, video: torch.Tensor, slab: torch.Tensor = None) -> torch.Tensor:
         """video [3,F,H,W] replicated on every rank -- or slab [3,F,H/P,W]: only this rank's rows (rank * H/P ...), the halo rows of the
@@ -1064,8 +710,7 @@ class AutoencoderKLWan:
         plan = encoder_plan()
         if slab is not None:
             C, Fr, Hs, Wd = slab.shape
-            H = Hs * P
-            xpad = self._halo_pad(self._video_in(slab))
+            xpad = self._halo_pad(self._video_in(slab), 1)
         else:
             C, Fr, H, Wd = video.shape
             Hs = H // P
@@ -1075,42 +720,23 @@ class AutoencoderKLWan:
             xpad = self._rows_from_full(xs, y0 - 1 - lo, y0 + Hs + 1 - lo)
         kind, p, cin, cout = plan[0]
         x, _ = self._conv(xpad, p, Fr, Hs, Wd, cout, (3, 3, 3), pt=2, ps=1, ph=0)
-        downs = [i for i, e in enumerate(plan) if e[0] in ("down2d", "down3d")]
-        last_down = downs[-1]
-        for kind, p, cin, cout in plan[1:last_down]:
-            if kind == "res":
-                x = self._res_slab(x, p, cin, cout)
-            else:
-                x = self._down_slab(x, p, cin, kind == "down3d")
-        x = self._gather_rows(x)                                # whole frames at the resolution of the last downsample
+        last_down = max(i for i, e in enumerate(plan) if e[0] in ("down2d", "down3d"))
+        x = self._gather_rows(self._run(x, plan[1:last_down], 1))   # whole frames at the resolution of the last downsample
         G = self._row_groups(x.shape[1], even=True)
-        if G > 1:
-            # the last downsample and everything after it (4 residual blocks, the mid-block attention, the head) in G row groups
-            self._reps = P // G
-            try:
-                g, Hg = rank // self._reps, x.shape[1] // G
-                x = x[:, g * Hg:(g + 1) * Hg].contiguous()
-                for kind, p, cin, cout in plan[last_down:]:
-                    if kind == "res":
-                        x = self._res_slab(x, p, cin, cout)
-                    elif kind in ("down2d", "down3d"):
-                        x = self._down_slab(x, p, cin, kind == "down3d")
-                    elif kind == "attn":
-                        x = self._attn_group(x, p, g, x.shape[1])
-                    else:  # head
-                        Tn, Hn, Wn, _ = x.shape
-                        a = self._halo_operand(x, self.w[p + ".0.gamma"])
-                        x, _ = self._conv(a, p + ".2", Tn, Hn, Wn, (cout + 31) // 32 * 32, (3, 3, 3), pt=2, ps=1, ph=0)
-                y = self._gather_rows(x)
-            finally:
-                self._reps = 1
-        else:
-            y = self._run(x, plan[last_down:])
+        if G == 1:
+            return self._moments(self._run(x, plan[last_down:]))
+        # the last downsample and everything after it (4 residual blocks, the mid-block attention, the head) in G row groups
+        k = P // G
+        g, Hg = rank // k, x.shape[1] // G
+        return self._moments(self._gather_rows(self._run(x[:, g * Hg:(g + 1) * Hg].contiguous(), plan[last_down:], k, g), k))
+
+    def _moments(self, y):
+        """quant conv1 on the encoder head's output y [T,h,w,32] -> [mean | logvar] as [32,T,h,w] f32."""
         T, h, w, _ = y.shape
         q = self._small_conv(y, "conv1", T, h, w, 2 * Z_DIM, (1, 1, 1))
         out = torch.empty((2 * Z_DIM, T, h, w), dtype=F32, device=self.device)
         call("wf_cl_to_ncthw", q.data_ptr(), out.data_ptr(), 2 * Z_DIM, 2 * Z_DIM, T * h * w, 0.0, ops.stream())
-        return out  # [mean | logvar]
+        return out
 
     def _video_in(self, video):
         """[3,F,H,W] f32 -> channels-last conv operand [F,H,W,32 (x3)]: 3 channels zero-padded to one MFMA K slice."""
@@ -1137,7 +763,7 @@ class AutoencoderKLWan:
     # diffusers protocol
     # ------------------------------------------------------------------------------------------------------------
     def _encode_one(self, video: torch.Tensor) -> torch.Tensor:
-        """[3,F,H,W] f32 -> posterior mean [16,T,h,w] f32  (vae.py:516-542 without the scale; mode() = mean half)."""
+        """[3,F,H,W] f32 -> posterior moments [32,T,h,w] f32  (vae.py:516-542 without the scale; mode() = mean half)."""
         C, Fr, H, Wd = video.shape
         if (Fr - 1) % 4 != 0:
             raise ValueError(f"number of frames must be 1 + 4k, got {Fr}")
@@ -1146,35 +772,37 @@ class AutoencoderKLWan:
         self.flops_last = 0
         if self.can_shard(H // 8):
             return self._encode_one_sharded(video)
-        x = self._video_in(video)
-        y = self._run(x, encoder_plan())
-        T, h, w, _ = y.shape
-        q = self._small_conv(y, "conv1", T, h, w, 2 * Z_DIM, (1, 1, 1))
-        out = torch.empty((2 * Z_DIM, T, h, w), dtype=F32, device=self.device)
-        call("wf_cl_to_ncthw", q.data_ptr(), out.data_ptr(), 2 * Z_DIM, 2 * Z_DIM, T * h * w, 0.0, ops.stream())
-        return out  # [mean | logvar]
+        return self._moments(self._run(self._video_in(video), encoder_plan()))
 
-    def _decode_one(self, z: torch.Tensor, crop=None) -> torch.Tensor:
-        """[16,T,h,w] f32 -> [3, 4T-3, 8h, 8w] f32 clamped to [-1,1] (vae.py:544-568, autoencoder_kl_wan.py:1222).  crop = (a0, a1): see
-        decode(columns=...)."""
+    def _decode_one(self, z: torch.Tensor, crop=None, gather: bool = True) -> torch.Tensor:
+        """[16,T,h,w] f32 -> [3, 4T-3, 8h, 8w] f32 clamped to [-1,1] (vae.py:544-568, autoencoder_kl_wan.py:1222).  crop = (a0, a1): the
+        latent columns decoded after the latent-resolution stage, see decode(columns=...).  Row-sharded (can_shard): gather=False returns
+        this rank's row slab [3, F, 8h/P, 8w] (rows rank * 8h/P ...) instead of the gathered video."""
         C, T, h, w = z.shape
         self.flops_last = 0
-        if self.can_shard(h):
-            return self._decode_one_sharded(z, crop=crop)
+        shard = self.can_shard(h)
         x = torch.empty((T, h, w, Z_DIM), dtype=F32, device=self.device)
         call("wf_ncthw_to_cl", z.data_ptr(), x.data_ptr(), None, Z_DIM, Z_DIM, T * h * w, ops.stream())
         x = self._latent_in(x, T, h, w)  # 16 channels + 16 zero channels
         plan = decoder_plan()
-        if crop is None:
-            y = self._run(x, plan)
-        else:
-            first_up = next(i for i, e in enumerate(plan) if e[0] in ("up2d", "up3d"))
-            x = self._run(x, plan[:first_up])                       # the latent-resolution stage sees whole frames (mid-block attention)
-            y = self._run(x[:, :, crop[0]:crop[1]].contiguous(), plan[first_up:])
+        up0 = first_up(plan)
+        # the latent-resolution stage sees whole frames (mid-block attention)
+        x = self._decode_stage0_sharded(x, plan[:up0]) if shard else self._run(x, plan[:up0])
+        if crop is not None:
+            x = x[:, :, crop[0]:crop[1]].contiguous()
+        y = self._decode_ups_sharded(x, plan[up0:]) if shard else self._run(x, plan[up0:])
         Fo, Ho, Wo, Cy = y.shape
         out = torch.empty((3, Fo, Ho, Wo), dtype=F32, device=self.device)
         call("wf_cl_to_ncthw", y.data_ptr(), out.data_ptr(), 3, Cy, Fo * Ho * Wo, 1.0, ops.stream())
+        if shard and gather:
+            # one all-gather of the 3-channel slabs (round 5 gathered the padded 32-channel slabs, 4.1 GB at C2, and converted the whole video
+            # on every rank)
+            P = self.comm.world
+            allr = torch.empty((P, 3, Fo, Ho, Wo), dtype=F32, device=self.device)
+            self.comm.all_gather(allr, out)
+            out = allr.permute(1, 2, 0, 3, 4).reshape(3, Fo, P * Ho, Wo).contiguous()
         return out if crop is None else self._uncrop(out, crop, w)
+
 
     # ------------------------------------------------------------------------------------------------------------
     # decoding only what an IRR injection consumes
@@ -1194,7 +822,8 @@ class AutoencoderKLWan:
 
     def needed_columns(self, mask: torch.Tensor):
         """mask [1,1,F,H,W] f32 (aligned to the decoded size) -> (c0, c1): the LATENT columns whose pixels the blend can see (mask != 1
-        somewhere in the column), or None when that is (nearly) everything.  One 8-byte read-back per distinct mask tensor (the mask of a job
+        somewhere in the column), or (0, 0) when there is none: no pixel of the decoded video reaches the result then.  Whether a range is worth
+        cropping to is _crop_range's decision.  One 8-byte read-back per distinct mask tensor (the mask of a job
         is the same object for all its injections)."""
         key = (mask.data_ptr(), mask._version, tuple(mask.shape))
         cache = self.__dict__.setdefault("_cols_cache", {})
@@ -1255,8 +884,7 @@ class AutoencoderKLWan:
         if z.shape[0] != 1 or not self.can_shard(z.shape[3]):
             dec = self.decode(z, return_dict=False, columns=cols)[0]
             return self.encode(ops.blend_pixels(ref, mask, dec)).latent_dist
-        self.flops_last = 0
-        slab = self._io_out(self._decode_one_sharded(z[0], gather=False, crop=self._crop_range(cols, z.shape[4])))  # [3, F, Hs, W] in the module dtype
+        slab = self._io_out(self._decode_one(z[0], self._crop_range(cols, z.shape[4]), gather=False))  # [3, F, Hs, W] in the module dtype
         Hs = slab.shape[2]
         y0 = self.comm.rank * Hs
         fused = ops.blend_pixels(self._row_slab_of(ref, y0, Hs), self._row_slab_of(mask, y0, Hs), slab.unsqueeze(0))
