@@ -1,9 +1,10 @@
-"""Digest of every way the LongCat and the Wan DiT forwards and the VAE can run: for comparing two checkouts bit for bit and launch for launch.
+"""Digest of every way the LongCat and the Wan DiT forwards, the VAE and the two samplers can run: for comparing two checkouts bit for bit and
+launch for launch.
 
     python tools/forward_digest.py [--only PREFIX] [--dump DIR] > digest.txt
 
-One seeded random model of the multirank tests' size runs each path on a small grid (the Wan cases are named `wan.`..., the VAE's `vae.`...;
-`--only wan.` selects them); per case (and per simulated rank) one line (the VAE's with flops=<flops_last> behind it):
+One seeded random model of the multirank tests' size runs each path on a small grid (the Wan cases are named `wan.`..., the VAE's `vae.`...,
+the samplers' `pipe.lc.`... and `pipe.wan.`...; `--only wan.` selects the Wan cases); per case (and per simulated rank) one line (the VAE's with flops=<flops_last> behind it):
 
     <case> out=<sha256> calls=<n> launches=<sha256> trace=<sha256>
 
@@ -459,6 +460,167 @@ for _prec in ("bf16", "fp16x3", "bf16x3", "fp16"):
     for _P in (1, 2):
         for _what in ("encode", "decode"):
             CASES[f"vae.{_prec}.P{_P}.H64.T1.{_what}"] = _vae_case(_prec, _what, 64, T=1, P=_P)
+
+
+# ---- the two samplers (`pipe.`...): a seeded small real DiT and the real scheduler behind tests.fakes.FakeVAE, a CPU generator, 3 steps.
+# Every case traces the job twice, once for the frames ("np") and once for output_type="latent" --------------------------------------------
+def _both_outputs(job):
+    """job(output_type) -> what it returns -> [the frames as a tensor, the latents]."""
+    return lambda: [torch.from_numpy(job("np")), job("latent")]
+
+
+def _prompts(n=24):
+    """-> (positive, negative) embeddings [1, 1, n, 64] and their masks [1, n]."""
+    pe, ne = (_rand((1, 1, n, 64), 7) * 0.5).to(BF), (_rand((1, 1, n, 64), 8) * 0.5).to(BF)
+    pm, nm = torch.zeros(1, n, dtype=torch.int64), torch.zeros(1, n, dtype=torch.int64)
+    pm[:, :19] = 1
+    nm[:, :7] = 1
+    return pe, ne, pm, nm
+
+
+def _guide(Fr, H, W):
+    from tests.fakes import synthetic_ref_and_mask
+    ref, mask = synthetic_ref_and_mask(Fr, H, W)
+    return dict(video_ref=ref, mask=mask, guided=True, resample_steps=2, guide_steps=2, resample_round=2, use_pca_channel_selection=True,
+                static=True)
+
+
+def _lc_pipe(m, vae_dtype=torch.float32):
+    from tests.fakes import FakeVAE
+    from worldforge_amd.longcat_pipeline import LongCatVideoPipeline
+    from worldforge_amd.longcat_scheduler import FlowMatchEulerDiscreteScheduler
+    return LongCatVideoPipeline(FakeVAE(vae_dtype), FlowMatchEulerDiscreteScheduler(shift=3.0, flow_backend="tdiff"), m, device=DEV)
+
+
+def _lc_i2v(guidance=1.0, guided=False, P=1, **kw):
+    """generate_i2v on the latent grid (3, 16, 20).  P = 2: `cfg_split`, one CFG sample per simulated rank."""
+    def run():
+        Fr, H, W = 9, 128, 160
+        m0 = _model()
+        pe, ne, pm, nm = _prompts()
+        image = torch.rand(3, H, W, generator=torch.Generator().manual_seed(3))
+        extra = dict(_guide(Fr, H, W) if guided else {}, **kw)
+
+        def go(world=None):
+            m = m0
+            if world is not None:
+                m = LongCatVideoTransformer3DModel(m0.cfg, DEV)
+                m.w = m0.w
+            pipe = _lc_pipe(m)
+            if world is not None:
+                pipe.cfg_split = (world, world.split(2).group_index)
+            return _both_outputs(lambda ot: pipe.generate_i2v(
+                image=image, height=H, width=W, prompt_embeds=pe, prompt_attention_mask=pm, negative_prompt_embeds=ne,
+                negative_prompt_attention_mask=nm, num_frames=Fr, num_inference_steps=3, guidance_scale=guidance,
+                generator=torch.Generator().manual_seed(42), output_type=ot, **extra))()
+
+        if P == 1:
+            return _single(go)
+        return [(f".rank{r}", out, trace) for r, (out, trace) in enumerate(_run_ranks(P, go))]
+    return run
+
+
+CASES["pipe.lc.i2v.nocfg"] = _lc_i2v()
+CASES["pipe.lc.i2v.cfg"] = _lc_i2v(4.0)
+CASES["pipe.lc.i2v.guided_dsg"] = _lc_i2v(4.0, guided=True)
+CASES["pipe.lc.i2v.distill"] = _lc_i2v(use_distill=True)
+CASES["pipe.lc.i2v.cfg_split.ranks2"] = _lc_i2v(4.0, P=2)
+
+
+def _lc_vc(use_kv_cache, guidance):
+    """generate_vc on the latent grid (4, 8, 12): 2 condition and 2 noise frames."""
+    def run():
+        m = _model(depth=3, seed=4)
+        pe, ne, pm, nm = _prompts()
+        video = torch.rand(3, 9, 64, 96, generator=torch.Generator().manual_seed(3))
+        pipe = _lc_pipe(m)
+        return _single(_both_outputs(lambda ot: pipe.generate_vc(
+            video, 64, 96, pe, pm, negative_prompt_embeds=ne, negative_prompt_attention_mask=nm, num_frames=13, num_cond_frames=5,
+            num_inference_steps=3, guidance_scale=guidance, generator=torch.Generator().manual_seed(42), output_type=ot,
+            use_kv_cache=use_kv_cache)))
+    return run
+
+
+for _use in (True, False):
+    for _g in (1.0, 4.0):
+        CASES[f"pipe.lc.vc.{'cached' if _use else 'uncached'}.{'cfg' if _g > 1 else 'nocfg'}"] = _lc_vc(_use, _g)
+
+
+def _lc_refine(cond=None, vae_dtype=torch.float32, **kw):
+    """generate_refine of 5 stage-1 frames of 64 x 64 to 128 x 128 (4 latent frames of 8 x 8 tokens per block of the (4, 4, 8) chunks), 4
+    inference steps cut at t_thresh = 0.5.  cond: None, "image" or "video"."""
+    def run():
+        m = _model(seed=6, enable_bsa=True, bsa_params=_bsa_params())
+        pe, _, pm, _ = _prompts()
+        g = torch.Generator().manual_seed(3)
+        stage1 = (torch.rand(5, 64, 64, 3, generator=g) * 255).to(torch.uint8)
+        given = {None: {}, "image": dict(image=torch.rand(3, 128, 128, generator=g), num_cond_frames=1),
+                 "video": dict(video=(torch.rand(7, 128, 128, 3, generator=g) * 255).to(torch.uint8), num_cond_frames=5)}[cond]
+        pipe = _lc_pipe(m, vae_dtype)
+        return _single(_both_outputs(lambda ot: pipe.generate_refine(
+            stage1, 128, 128, pe, pm, num_inference_steps=4, generator=torch.Generator().manual_seed(42), output_type=ot, **given, **kw)))
+    return run
+
+
+CASES["pipe.lc.refine.plain"] = _lc_refine()
+CASES["pipe.lc.refine.image"] = _lc_refine("image")
+CASES["pipe.lc.refine.video.cached"] = _lc_refine("video", use_kv_cache=True)
+CASES["pipe.lc.refine.video.uncached"] = _lc_refine("video")
+CASES["pipe.lc.refine.spatial_only"] = _lc_refine("image", spatial_refine_only=True)
+CASES["pipe.lc.refine.vae_bf16"] = _lc_refine("image", vae_dtype=BF)
+
+
+class _NoPairMethod:
+    """A Wan DiT without forward_cfg_pair: the sampler then makes two plain calls."""
+
+    def __init__(self, m):
+        self._m, self.dtype = m, m.dtype
+
+    def __call__(self, *a, **k):
+        return self._m(*a, **k)
+
+
+def _wan_pipe_case(guidance=1.0, guided=False, P=1, no_pair=False, latent_only=False, **kw):
+    """WanImageToVideoPipeline.__call__ on the latent grid (3, 16, 20).  P = 2: `cfg_split`, one CFG branch per simulated rank."""
+    def run():
+        from tests.fakes import FakeVAE
+        from worldforge_amd.pipeline import WanImageToVideoPipeline
+        from worldforge_amd.scheduler import UniPCMultistepScheduler
+        Fr, H, W = 9, 128, 160
+        m0 = _wan_model()
+        text, neg, img = (_rand((1, 30, 64), 7) * 0.5).to(BF), (_rand((1, 30, 64), 8) * 0.5).to(BF), _rand((1, 257, 1280), 9).to(BF)
+        image = torch.rand(3, H, W, generator=torch.Generator().manual_seed(3))
+        extra = dict(_guide(Fr, H, W) if guided else {}, **kw)
+
+        def go(world=None):
+            m = m0
+            if world is not None:
+                m = WanTransformer3DModel(m0.cfg, DEV)
+                m.w = m0.w
+            pipe = WanImageToVideoPipeline(_NoPairMethod(m) if no_pair else m, FakeVAE(),
+                                           UniPCMultistepScheduler(flow_shift=3.0, flow_backend="tdiff"), device=DEV)
+            if world is not None:
+                pipe.cfg_split = (world, world.split(2).group_index)
+
+            def job(ot):
+                return pipe(image=image, height=H, width=W, num_frames=Fr, num_inference_steps=3, guidance_scale=guidance,
+                            generator=torch.Generator().manual_seed(42), prompt_embeds=text, negative_prompt_embeds=neg,
+                            image_embeds=img, output_type=ot, return_dict=False, **extra)[0]
+            return job("latent") if latent_only else _both_outputs(job)()
+
+        if P == 1:
+            return _single(go)
+        return [(f".rank{r}", out, trace) for r, (out, trace) in enumerate(_run_ranks(P, go))]
+    return run
+
+
+CASES["pipe.wan.nocfg"] = _wan_pipe_case()
+CASES["pipe.wan.cfg_pair"] = _wan_pipe_case(4.0)
+CASES["pipe.wan.cfg_two_calls"] = _wan_pipe_case(4.0, no_pair=True)
+CASES["pipe.wan.guided_dsg"] = _wan_pipe_case(4.0, guided=True)
+CASES["pipe.wan.cfg_split.ranks2"] = _wan_pipe_case(4.0, P=2)
+CASES["pipe.wan.window"] = _wan_pipe_case(4.0, start_step=1, max_steps=2)
+CASES["pipe.wan.latent"] = _wan_pipe_case(latent_only=True)
 
 
 def main():

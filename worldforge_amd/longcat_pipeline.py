@@ -19,6 +19,20 @@ import numpy as np
 import torch
 
 from . import ops
+from . import sampler_common as sc
+
+
+def prompt_batch(device, dtype, prompt_embeds, prompt_attention_mask, negative_prompt_embeds=None, negative_prompt_attention_mask=None,
+                 do_cfg: bool = False):
+    """The prompt hand-off: -> (embeddings in `dtype`, attention masks) on `device`; under CFG the batch [negative, positive] of both
+    (PIPE:760-762 / 1148-1150)."""
+    pe, pm = prompt_embeds.to(device, dtype), prompt_attention_mask.to(device)
+    if do_cfg:
+        if negative_prompt_embeds is None:
+            raise ValueError("classifier-free guidance (guidance_scale > 1) needs the negative prompt embeddings")
+        pe = torch.cat([negative_prompt_embeds.to(device, dtype), pe], dim=0)
+        pm = torch.cat([negative_prompt_attention_mask.to(device), pm], dim=0)
+    return pe, pm
 
 
 class LongCatVideoPipeline:
@@ -72,30 +86,40 @@ class LongCatVideoPipeline:
             sigmas = torch.linspace(0.999, 0.000, sampling_steps)
         return sigmas.to(torch.float32)
 
-    def _preprocess_image(self, image, height, width) -> torch.Tensor:
-        """diffusers VideoProcessor.preprocess: -> [1,3,H,W] fp32 in [-1,1]."""
-        if isinstance(image, torch.Tensor):
-            t = (image if image.dim() == 4 else image.unsqueeze(0)).to(torch.float32)
-        else:
-            if image.size != (width, height):
-                image = image.resize((width, height))
-            t = torch.from_numpy(np.array(image).astype(np.float32) / 255.0).permute(2, 0, 1).unsqueeze(0)
-        if t.shape[-2:] != (height, width):
-            raise ValueError(f"image tensor is {tuple(t.shape[-2:])}, expected {(height, width)}")
-        return 2.0 * t - 1.0
+    def _check_size(self, height: int, width: int, blocks: int = 1):
+        """PIPE:199-201 (and :1336, the refine pass: blocks = 4)."""
+        ssp = self.vae_scale_factor_spatial * 2 * blocks
+        if height % ssp != 0 or width % ssp != 0:
+            raise ValueError(f"`height and width` have to be divisible by {ssp} but are {height} and {width}.")
 
-    def _randn(self, shape, generator):
-        # diffusers / the reference draw on the CPU generator and move (RNG parity)
-        if generator is not None and generator.device.type == "cpu":
-            return torch.randn(shape, generator=generator).to(self.device)
-        return torch.randn(shape, generator=generator, device=self.device)
+    def _snap_frames(self, num_frames: int) -> int:
+        """PIPE:700-704 / 1092-1096: down to 4k + 1 frames."""
+        if num_frames % self.vae_scale_factor_temporal != 1:
+            num_frames = num_frames // self.vae_scale_factor_temporal * self.vae_scale_factor_temporal + 1
+        return max(num_frames, 1)
+
+    def _set_timesteps(self, num_inference_steps: int, use_distill: bool = False) -> torch.Tensor:
+        """PIPE:764-767 / 1152-1155 / 1394-1395."""
+        sigmas = self.get_timesteps_sigmas(num_inference_steps, use_distill=use_distill)
+        self.scheduler.set_timesteps(num_inference_steps, sigmas=sigmas, device=self.device)
+        return self.scheduler.timesteps
+
+    def _noise_latents(self, batch_size, num_channels_latents, height, width, num_frames, generator, latents):
+        """PIPE:214-256: the given latents on the device, or noise of the latent shape drawn in fp32."""
+        T = (num_frames - 1) // self.vae_scale_factor_temporal + 1
+        shape = (batch_size, num_channels_latents, T, height // self.vae_scale_factor_spatial, width // self.vae_scale_factor_spatial)
+        return sc.randn(shape, generator, self.device) if latents is None else latents.to(self.device)
+
+    def _norm_in_own_dtype(self, x: torch.Tensor) -> torch.Tensor:
+        """PIPE:385-394 as the reference writes it: the constants and both statements in x's dtype (ops.latent_norm is the fp32 form)."""
+        mean = torch.tensor(self.vae.config.latents_mean).view(1, -1, 1, 1, 1).to(self.device, x.dtype)
+        istd = 1.0 / torch.tensor(self.vae.config.latents_std).view(1, -1, 1, 1, 1).to(self.device, x.dtype)
+        return (x - mean) * istd
 
     # ---- PIPE:214-286 with num_cond_frames = 1 ----------------------------------------------------------------------------
     def prepare_latents(self, image: torch.Tensor, batch_size: int, num_channels_latents: int, height: int, width: int,
                         num_frames: int, generator=None, latents: Optional[torch.Tensor] = None) -> torch.Tensor:
-        T = (num_frames - 1) // self.vae_scale_factor_temporal + 1
-        shape = (batch_size, num_channels_latents, T, height // self.vae_scale_factor_spatial, width // self.vae_scale_factor_spatial)
-        latents = self._randn(shape, generator).to(torch.float32) if latents is None else latents.to(self.device, torch.float32)
+        latents = self._noise_latents(batch_size, num_channels_latents, height, width, num_frames, generator, latents).to(torch.float32)
         cond = []
         for i in range(batch_size):
             post = self.vae.encode(image[i].unsqueeze(0).unsqueeze(2)).latent_dist
@@ -110,19 +134,14 @@ class LongCatVideoPipeline:
                               latents: Optional[torch.Tensor] = None) -> torch.Tensor:
         """video [B, 3, F, H, W] in [-1, 1]: its LAST num_cond_frames frames are encoded (PIPE:272), sampled, normalised in `dtype`
         (PIPE:280-281: generate_vc holds its latents in the DiT dtype) and written over the first latent frames of the noise."""
-        T = (num_frames - 1) // self.vae_scale_factor_temporal + 1
-        shape = (batch_size, num_channels_latents, T, height // self.vae_scale_factor_spatial, width // self.vae_scale_factor_spatial)
-        latents = (self._randn(shape, generator) if latents is None else latents.to(self.device)).to(dtype)  # PIPE:234, 252
+        latents = self._noise_latents(batch_size, num_channels_latents, height, width, num_frames, generator, latents).to(dtype)  # PIPE:234, 252
         cond = []
         for i in range(batch_size):
             enc_in = video[i][:, -num_cond_frames:].unsqueeze(0)
             assert enc_in.shape[2] == num_cond_frames, "the video has fewer frames than num_cond_frames"  # PIPE:276
             cond.append(self.vae.encode(enc_in).latent_dist.sample(generator))
-        cond = torch.cat(cond, dim=0).to(self.device, dtype)
-        mean = torch.tensor(self.vae.config.latents_mean).view(1, -1, 1, 1, 1).to(self.device, dtype)  # PIPE:385-394 in `dtype`
-        istd = 1.0 / torch.tensor(self.vae.config.latents_std).view(1, -1, 1, 1, 1).to(self.device, dtype)
         ncl = 1 + (num_cond_frames - 1) // self.vae_scale_factor_temporal
-        latents[:, :, :ncl] = (cond - mean) * istd
+        latents[:, :, :ncl] = self._norm_in_own_dtype(torch.cat(cond, dim=0).to(self.device, dtype))
         return latents
 
     def _preprocess_video(self, video, height, width) -> torch.Tensor:
@@ -138,6 +157,83 @@ class LongCatVideoPipeline:
             raise ValueError(f"video is {tuple(v.shape)}, expected [1, 3, F, {height}, {width}] (resizing to the bucket belongs to the front-end)")
         return 2.0 * v - 1.0
 
+    # ---- the stages the three passes share -------------------------------------------------------------------------------------
+    def _dit_forward(self, num_cond_latents: int, split=None):
+        """-> forward(x, ts, pe, pm) for _velocity: the DiT's plain call on all frames, the first num_cond_latents of them clean.  With
+        split (generate_i2v's `cfg_split`): the CFG batch [negative, positive] of PIPE:857-866 is two samples, and group b of the job's
+        ranks runs sample b as ONE such call (sampler_common.cfg_groups_exchange)."""
+        def plain(x, ts, pe, pm):
+            return self.dit(hidden_states=x, timestep=ts, encoder_hidden_states=pe, encoder_attention_mask=pm,
+                            num_cond_latents=num_cond_latents)
+
+        def grouped(x, ts, pe, pm):
+            if x.shape[0] != 2:
+                return plain(x, ts, pe, pm)
+            return torch.cat(sc.cfg_groups_exchange(split, lambda b: plain(x[b:b + 1], ts[b:b + 1], pe[b:b + 1], pm[b:b + 1])))
+
+        return plain if split is None else grouped
+
+    def _velocity(self, forward, latents, t, pe, pm, cfg_scale: Optional[float], num_clean: int) -> torch.Tensor:
+        """PIPE:852-888 / 1206-1242 / 1466-1489: what the scheduler steps along.  The latents go to the DiT in its dtype, twice under CFG
+        (cfg_scale is not None: pe / pm are then the batch [negative, positive]), with the timestep in that dtype, one per latent
+        frame and t = 0 on the first num_clean frames; forward(x, ts, pe, pm) is the DiT call (_dit_forward, or a cached forward bound
+        to its cache).  Then CFG-zero (PIPE:875-885) and the sign flip of PIPE:888 in one launch per sample, or the plain negation."""
+        dit_dtype = self.dit.dtype
+        x_in = ops.cast(latents, dit_dtype)
+        if cfg_scale is not None:
+            x_in = torch.cat([x_in] * 2)
+        ts = t.expand(x_in.shape[0]).to(dit_dtype).unsqueeze(-1).repeat(1, x_in.shape[2])
+        if num_clean:
+            ts[:, :num_clean] = 0
+        noise_pred = forward(x_in, ts, pe, pm)
+        if cfg_scale is None:
+            return -noise_pred
+        u, c = noise_pred.chunk(2)
+        return torch.stack([ops.cfg_zero(c[b], u[b], cfg_scale, negate=True) for b in range(c.shape[0])])
+
+    def _denoise_window(self, latents, ncl: int, timesteps, pe, pm, cfg_scale, step_hook, cached=None) -> torch.Tensor:
+        """The loop of generate_vc (PIPE:1195-1255) and generate_refine (PIPE:1464-1497): the first ncl latent frames are the clean
+        condition, the rest are denoised.  cached = (build, forward), the DiT's cache_condition / forward_cached or their _blocks
+        forms: the condition frames go through the DiT once (one video per call: a CFG pair shares the cache, LCA:163-165), every
+        step runs and steps the noise frames only (PIPE:1246), and the condition is put back in front (PIPE:1254-1255).  cached =
+        None: every step runs all frames through the plain call (PIPE:1215-1216) and steps the noise frames in place (PIPE:1248),
+        which rounds them to the dtype the latents are held in."""
+        sch = self.scheduler
+        cond_latents = None
+        if cached is None:
+            forward = self._dit_forward(ncl)
+        else:
+            build, cached_forward = cached
+            cond_latents = latents[:, :, :ncl]
+            cache = build(cond_latents[0])
+            latents = latents[:, :, ncl:].contiguous()
+
+            def forward(x, ts, pe, pm):
+                return cached_forward(x, ts, pe, pm, cache)
+        for i, t in enumerate(timesteps):
+            if step_hook is not None:
+                step_hook(i, "start")
+            sch.derivative_history = []  # (the scheduler notes every velocity it steps along; only generate_i2v reads them)
+            noise_pred = self._velocity(forward, latents, t, pe, pm, cfg_scale, 0 if cached else ncl)
+            if cached:
+                latents = sch.step(noise_pred, t, latents, return_dict=False)[0]
+            else:
+                latents[:, :, ncl:] = sch.step(noise_pred[:, :, ncl:], t, latents[:, :, ncl:], return_dict=False)[0]
+            if step_hook is not None:
+                step_hook(i, "end")
+        return latents if cond_latents is None else torch.cat([cond_latents, latents], dim=2)
+
+    def _final_latents(self, latents: torch.Tensor) -> torch.Tensor:
+        """PIPE:999-1000: `latents.to(self.vae.dtype)` and the de-normalisation IN THAT DTYPE (a bf16 VAE module, the LongCat entry's
+        run_longcat_worldforge_single.py:205: constants and both statements in bf16), handed to decode in the module dtype."""
+        vdt = getattr(self.vae, "dtype", torch.float32)
+        z = ops.latent_denorm(ops.cast(latents, vdt), self.vae.config.latents_mean, self.vae.config.latents_std)  # f32 holding vdt values
+        return z if vdt == torch.float32 else ops.cast(z, vdt)
+
+    def _finish(self, latents: torch.Tensor, output_type: str, crop=None):
+        """PIPE:996-1006: the latents, or the decoded frames [B,F,H,W,C] in [0,1]."""
+        return sc.decode_tail(self.vae, latents, output_type, self._final_latents, crop=crop)
+
     # ---- PIPE:1010-1267 ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate_vc(self, video, height: int, width: int, prompt_embeds: torch.Tensor, prompt_attention_mask: torch.Tensor,
@@ -147,84 +243,35 @@ class LongCatVideoPipeline:
                     use_kv_cache: bool = True, offload_kv_cache: bool = False, enhance_hf: bool = False, step_hook=None):
         """Video continuation: the last num_cond_frames frames of `video` become the first num_cond_latents = 1 + (num_cond_frames - 1)
         // 4 latent frames, kept clean (timestep 0) while the remaining frames are denoised; the result is a num_frames video that
-        starts with them.  use_kv_cache (the default, PIPE:1195-1199): the condition frames go through the DiT ONCE
-        (dit.cache_condition), every step then runs the noise frames only on that resident cache (dit.forward_cached), and the
-        condition latents are put back in front at the end (PIPE:1254-1255).  use_kv_cache=False: every step runs all frames through
-        the plain call (PIPE:1215-1216) and steps the noise frames (PIPE:1248).  CFG-zero and the distilled schedule as in
-        generate_i2v.  The latents are held in the DiT dtype as the reference's are (PIPE:1181), so the uncached loop rounds them to
-        it after every step (PIPE:1248 writes into them) while the cached loop carries the scheduler's fp32 result (PIPE:1246).
+        starts with them.  use_kv_cache (the default, PIPE:1195-1199): the loop runs on the DiT's resident condition cache
+        (dit.cache_condition / dit.forward_cached, see _denoise_window); use_kv_cache=False: on all frames.  CFG-zero and the
+        distilled schedule as in generate_i2v.  The latents are held in the DiT dtype as the reference's are (PIPE:1181), so the
+        uncached loop rounds them to it after every step (PIPE:1248 writes into them) while the cached loop carries the scheduler's
+        fp32 result (PIPE:1246).
         Not built: offload_kv_cache (the cache stays on the GPU), enhance_hf (the 10-step uniform tail of PIPE:1157-1166; the
         reference's default), several videos per prompt."""
         if offload_kv_cache:
             raise NotImplementedError("offload_kv_cache: the condition cache stays on the GPU")
         if enhance_hf:
             raise NotImplementedError("enhance_hf (PIPE:1157-1166) is not built")
-        dev, sch = self.device, self.scheduler
-        ssp = self.vae_scale_factor_spatial * 2
-        if height % ssp != 0 or width % ssp != 0:
-            raise ValueError(f"`height and width` have to be divisible by {ssp} but are {height} and {width}.")  # PIPE:199-201
-        if num_frames % self.vae_scale_factor_temporal != 1:
-            num_frames = num_frames // self.vae_scale_factor_temporal * self.vae_scale_factor_temporal + 1  # PIPE:1092-1096
-        num_frames = max(num_frames, 1)
+        self._check_size(height, width)
+        num_frames = self._snap_frames(num_frames)
         ncl = 1 + (num_cond_frames - 1) // self.vae_scale_factor_temporal  # PIPE:1189
         if num_cond_frames < 1 or ncl >= (num_frames - 1) // self.vae_scale_factor_temporal + 1:
             raise ValueError(f"num_cond_frames = {num_cond_frames} must be >= 1 and leave at least one of the {num_frames} frames to generate")
         self._guidance_scale = guidance_scale
         do_cfg = self.do_classifier_free_guidance
         dit_dtype = self.dit.dtype
-        pe = prompt_embeds.to(dev, dit_dtype)
-        pm = prompt_attention_mask.to(dev)
-        if do_cfg:
-            if negative_prompt_embeds is None:
-                raise ValueError("classifier-free guidance (guidance_scale > 1) needs the negative prompt embeddings")
-            pe = torch.cat([negative_prompt_embeds.to(dev, dit_dtype), pe], dim=0)  # PIPE:1148-1150
-            pm = torch.cat([negative_prompt_attention_mask.to(dev), pm], dim=0)
-        # PIPE:1152-1155
-        sch.set_timesteps(num_inference_steps, sigmas=self.get_timesteps_sigmas(num_inference_steps, use_distill=use_distill), device=dev)
-        timesteps = sch.timesteps
+        pe, pm = prompt_batch(self.device, dit_dtype, prompt_embeds, prompt_attention_mask, negative_prompt_embeds,
+                              negative_prompt_attention_mask, do_cfg)
+        timesteps = self._set_timesteps(num_inference_steps, use_distill)
         # PIPE:1168-1185
-        vid = self._preprocess_video(video, height, width).to(dev, dit_dtype)
+        vid = self._preprocess_video(video, height, width).to(self.device, dit_dtype)
         latents = self.prepare_latents_video(vid, 1, self.dit.config.in_channels, height, width, num_frames, num_cond_frames, dit_dtype,
                                              generator, latents)
-        cache = None
-        if use_kv_cache:  # PIPE:1195-1199
-            cond_latents = latents[:, :, :ncl]
-            cache = self.dit.cache_condition(cond_latents[0])  # one video per call: the CFG pair shares it (LCA:163-165)
-            latents = latents[:, :, ncl:]
-        for i, t in enumerate(timesteps):  # PIPE:1204-1252
-            if step_hook is not None:
-                step_hook(i, "start")
-            sch.derivative_history = []
-            x_in = ops.cast(latents, dit_dtype)
-            if do_cfg:
-                x_in = torch.cat([x_in] * 2)
-            ts = t.expand(x_in.shape[0]).to(dit_dtype).unsqueeze(-1).repeat(1, x_in.shape[2])
-            if use_kv_cache:
-                noise_pred = self.dit.forward_cached(x_in, ts, pe, pm, cache)
-            else:
-                ts[:, :ncl] = 0
-                noise_pred = self.dit(hidden_states=x_in, timestep=ts, encoder_hidden_states=pe, encoder_attention_mask=pm,
-                                      num_cond_latents=ncl)
-            if do_cfg:  # CFG-zero (PIPE:1227-1239) and the sign flip of PIPE:1242 in one launch per sample
-                u, c = noise_pred.chunk(2)
-                noise_pred = torch.stack([ops.cfg_zero(c[b], u[b], guidance_scale, negate=True) for b in range(c.shape[0])])
-            else:
-                noise_pred = -noise_pred
-            if use_kv_cache:
-                latents = sch.step(noise_pred, t, latents, return_dict=False)[0]  # PIPE:1246
-            else:
-                latents[:, :, ncl:] = sch.step(noise_pred[:, :, ncl:], t, latents[:, :, ncl:], return_dict=False)[0]  # PIPE:1248
-            if step_hook is not None:
-                step_hook(i, "end")
-        if use_kv_cache:
-            latents = torch.cat([cond_latents, latents], dim=2)  # PIPE:1254-1255
-        if output_type == "latent":
-            self._check_vae_range()
-            return latents
-        video_out = self.vae.decode(self._final_latents(latents), return_dict=False)[0]
-        video_out = torch.stack([ops.postprocess_video(v) for v in video_out])  # [B,F,H,W,C] in [0,1]
-        self._check_vae_range()
-        return video_out.cpu().numpy() if output_type == "np" else video_out
+        latents = self._denoise_window(latents, ncl, timesteps, pe, pm, guidance_scale if do_cfg else None, step_hook,
+                                       (self.dit.cache_condition, self.dit.forward_cached) if use_kv_cache else None)
+        return self._finish(latents, output_type)
 
     # ---- PIPE:1271-1511 ---------------------------------------------------------------------------------------------------
     @staticmethod
@@ -256,6 +303,47 @@ class LongCatVideoPipeline:
         assert enc_in.shape[2] == num_cond_frames
         return enc_in
 
+    def _cut_schedule(self, timesteps: torch.Tensor, t_thresh: float) -> torch.Tensor:
+        """PIPE:1396-1402: the schedule entered at t_thresh."""
+        sch = self.scheduler
+        tt = torch.tensor(t_thresh * 1000, dtype=timesteps.dtype)
+        timesteps = torch.cat([tt.unsqueeze(0), timesteps[timesteps < tt]])
+        sch.timesteps = timesteps
+        sch.sigmas = torch.cat([timesteps / 1000, torch.zeros(1)])
+        return timesteps
+
+    def _upsample_stage1(self, stage1_video, height: int, width: int, spatial_refine_only: bool) -> torch.Tensor:
+        """PIPE:1404-1413: the up-sampling chain in the DiT dtype, one kernel.  uint8 frames [F, H0, W0, 3] -> [1, 3, F or 2 F, height,
+        width] fp32 in [-1, 1]."""
+        from ._ffi import call
+        frames = torch.as_tensor(np.array(stage1_video)) if not isinstance(stage1_video, torch.Tensor) else stage1_video
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+            raise ValueError("stage1_video must be uint8 frames [F, H, W, 3]")
+        if self.dit.dtype != torch.bfloat16:
+            raise NotImplementedError("the up-sampling kernel rounds as a bf16 model does")
+        frames = frames.to(self.device).contiguous()
+        nf, H0, W0, _ = frames.shape
+        new_frame_size = nf if spatial_refine_only else 2 * nf
+        up = torch.empty((1, 3, new_frame_size, height, width), dtype=torch.float32, device=self.device)
+        call("wf_refine_upsample_u8", frames.data_ptr(), up.data_ptr(), nf, H0, W0, new_frame_size, height, width, ops.stream())
+        return up
+
+    def _noised_latents(self, up: torch.Tensor, t_thresh: float, generator) -> torch.Tensor:
+        """PIPE:1426-1435: the up-sampled video encoded (posterior sample), normalised and mixed with noise: (1 - t) * latent + t * noise,
+        in fp32."""
+        dev = self.device
+        samp = self.vae.encode(up if getattr(self.vae, "dtype", torch.float32) == torch.float32 else ops.cast(up, self.vae.dtype)) \
+            .latent_dist.sample(generator).to(dev)
+        if samp.dtype == torch.float32:
+            lat = ops.latent_norm(samp, self.vae.config.latents_mean, self.vae.config.latents_std)
+            noise = sc.randn(tuple(lat.shape), generator, dev).to(lat.dtype)
+            return ops.add_noise(lat, noise, 1 - t_thresh, t_thresh)
+        # a bf16 VAE module hands back a bf16 sample: PIPE:1431-1433 then normalise in bf16 (constants in bf16), draw the noise IN BF16
+        # (a different stream of the generator than an fp32 draw) and mix in bf16; prepare_latents casts the result to fp32 (PIPE:234)
+        lat = self._norm_in_own_dtype(samp)
+        noise = sc.randn(lat.shape, generator, dev, lat.dtype)
+        return ((1 - t_thresh) * lat + t_thresh * noise).to(torch.float32)
+
     @torch.no_grad()
     def generate_refine(self, stage1_video, height: int, width: int, prompt_embeds: torch.Tensor, prompt_attention_mask: torch.Tensor,
                         image=None, num_cond_frames: int = 0, num_inference_steps: int = 50, generator=None, output_type: str = "np",
@@ -271,116 +359,43 @@ class LongCatVideoPipeline:
         default: the reference does not cache here): the condition latents go through the block-sparse DiT once
         (dit.cache_condition_blocks), every step runs the noise frames only (dit.forward_cached_blocks), and the condition latents
         are put back in front before decoding.  Returns frames [1, F', H, W, 3] in [0, 1]."""
-        from ._ffi import call
-        dev, sch = self.device, self.scheduler
         if image is not None and video is not None:  # PIPE:1332
             raise ValueError("Cannot provide both `image and video` at the same time. Please provide only one.")
         if video is not None and num_cond_frames <= 0:
             raise ValueError("a conditioning video needs num_cond_frames > 0 (how many of its last frames condition the window)")
         if use_kv_cache and num_cond_frames <= 0:
             raise ValueError("use_kv_cache caches the condition frames' stream: it needs num_cond_frames > 0 and an image or a video")
-        ssp = self.vae_scale_factor_spatial * 2 * 4  # PIPE:1336
-        if height % ssp != 0 or width % ssp != 0:
-            raise ValueError(f"`height and width` have to be divisible by {ssp} but are {height} and {width}.")
-        dit_dtype = self.dit.dtype
-        pe, pm = prompt_embeds.to(dev, dit_dtype), prompt_attention_mask.to(dev)
-        # PIPE:1394-1402: the schedule, cut at t_thresh
-        sch.set_timesteps(num_inference_steps, sigmas=self.get_timesteps_sigmas(num_inference_steps), device=dev)
-        timesteps = sch.timesteps
+        self._check_size(height, width, blocks=4)
+        dev, dit_dtype = self.device, self.dit.dtype
+        pe, pm = prompt_batch(dev,dit_dtype, prompt_embeds, prompt_attention_mask)
+        timesteps = self._set_timesteps(num_inference_steps)
         if t_thresh:
-            tt = torch.tensor(t_thresh * 1000, dtype=timesteps.dtype)
-            timesteps = torch.cat([tt.unsqueeze(0), timesteps[timesteps < tt]])
-            sch.timesteps = timesteps
-            sch.sigmas = torch.cat([timesteps / 1000, torch.zeros(1)])
-        # PIPE:1404-1413: up-sampling chain in the DiT dtype, one kernel
-        frames = torch.as_tensor(np.array(stage1_video)) if not isinstance(stage1_video, torch.Tensor) else stage1_video
-        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
-            raise ValueError("stage1_video must be uint8 frames [F, H, W, 3]")
-        if dit_dtype != torch.bfloat16:
-            raise NotImplementedError("the up-sampling kernel rounds as a bf16 model does")
-        frames = frames.to(dev).contiguous()
-        nf, H0, W0, _ = frames.shape
-        new_frame_size = nf if spatial_refine_only else 2 * nf
-        up = torch.empty((1, 3, new_frame_size, height, width), dtype=torch.float32, device=dev)
-        call("wf_refine_upsample_u8", frames.data_ptr(), up.data_ptr(), nf, H0, W0, new_frame_size, height, width, ops.stream())
+            timesteps = self._cut_schedule(timesteps, t_thresh)
+        up = self._upsample_stage1(stage1_video, height, width, spatial_refine_only)
+        new_frame_size = up.shape[2]
         # PIPE:1415-1435: pad to the block-sparse granularity (4 latent frames), encode, mix with noise
         ncl, added_c, nnl, added_n = self.refine_padding(num_cond_frames, new_frame_size, self.vae_scale_factor_temporal)
         num_cond_frames = num_cond_frames + added_c
         up = torch.cat([up[:, :, 0:1].repeat(1, 1, added_c, 1, 1), up, up[:, :, -1:].repeat(1, 1, added_n, 1, 1)], dim=2)
-        mean, std = self.vae.config.latents_mean, self.vae.config.latents_std
-        samp = self.vae.encode(up if getattr(self.vae, "dtype", torch.float32) == torch.float32 else ops.cast(up, self.vae.dtype)) \
-            .latent_dist.sample(generator).to(dev)
-        if samp.dtype == torch.float32:
-            lat = ops.latent_norm(samp, mean, std)
-            noise = self._randn(tuple(lat.shape), generator).to(lat.dtype)
-            latents = ops.add_noise(lat, noise, 1 - t_thresh, t_thresh)  # (1 - t) * latent + t * noise
-        else:
-            # a bf16 VAE module hands back a bf16 sample: PIPE:1431-1433 then normalise in bf16 (constants in bf16), draw the noise IN BF16
-            # (a different stream of the generator than an fp32 draw) and mix in bf16; prepare_latents casts the result to fp32 (PIPE:234)
-            m = torch.tensor(mean).view(1, -1, 1, 1, 1).to(dev, samp.dtype)
-            istd = 1.0 / torch.tensor(std).view(1, -1, 1, 1, 1).to(dev, samp.dtype)
-            lat = (samp - m) * istd
-            if generator is not None and generator.device.type == "cpu":
-                noise = torch.randn(lat.shape, generator=generator, dtype=lat.dtype).to(dev)
-            else:
-                noise = torch.randn(lat.shape, generator=generator, dtype=lat.dtype, device=dev)
-            latents = ((1 - t_thresh) * lat + t_thresh * noise).to(torch.float32)
-        del up, noise
-        if image is not None:  # PIPE:262-284: the condition frame, front-padded, encoded (posterior sample), normalised
-            img = self._preprocess_image(image, height, width).to(dev, dit_dtype)
+        latents = self._noised_latents(up, t_thresh, generator)
+        del up
+        enc_in = None
+        if image is not None:  # PIPE:262-284: the condition frame, front-padded
+            img = sc.preprocess_image(image, height, width).to(dev, dit_dtype)
             enc_in = img[0].unsqueeze(0).unsqueeze(2)
             enc_in = torch.cat([enc_in[:, :, 0:1].repeat(1, 1, added_c, 1, 1), enc_in], dim=2)
             assert enc_in.shape[2] == num_cond_frames
-            cond = self.vae.encode(enc_in).latent_dist.sample(generator).to(dev, torch.float32)
-            latents[:, :, :ncl] = ops.latent_norm(cond, mean, std)
         elif video is not None:  # PIPE:272-284: the last frames of the video, front-padded likewise
             vid = self._preprocess_video(video, height, width).to(dev, dit_dtype)
             enc_in = self.refine_condition_frames(vid, num_cond_frames, added_c)
-            cond = self.vae.encode(enc_in).latent_dist.sample(generator).to(dev, torch.float32)
-            latents[:, :, :ncl] = ops.latent_norm(cond, mean, std)
         elif num_cond_frames > 0:
             raise ValueError("num_cond_frames > 0 needs the conditioning image or the conditioning video")
-        cache = cond_latents = None
-        if use_kv_cache:
-            cond_latents = latents[:, :, :ncl]
-            cache = self.dit.cache_condition_blocks(cond_latents[0])
-            latents = latents[:, :, ncl:].contiguous()
-        # PIPE:1464-1497
-        for i, t in enumerate(timesteps):
-            if step_hook is not None:
-                step_hook(i, "start")
-            ts = t.expand(latents.shape[0]).to(dit_dtype).unsqueeze(-1).repeat(1, latents.shape[2])
-            if cache is not None:
-                noise_pred = -self.dit.forward_cached_blocks(ops.cast(latents, dit_dtype), ts, pe, pm, cache)
-                latents = sch.step(noise_pred, t, latents, return_dict=False)[0]
-            else:
-                ts[:, :ncl] = 0
-                noise_pred = -self.dit(hidden_states=ops.cast(latents, dit_dtype), timestep=ts, encoder_hidden_states=pe,
-                                       encoder_attention_mask=pm, num_cond_latents=ncl)
-                latents[:, :, ncl:] = sch.step(noise_pred[:, :, ncl:], t, latents[:, :, ncl:], return_dict=False)[0]
-            if step_hook is not None:
-                step_hook(i, "end")
-        if cache is not None:
-            latents = torch.cat([cond_latents, latents.to(cond_latents.dtype)], dim=2)
-        if output_type == "latent":
-            self._check_vae_range()
-            return latents
-        out = self.vae.decode(self._final_latents(latents), return_dict=False)[0]
-        video = torch.stack([ops.postprocess_video(v) for v in out])[:, added_c: new_frame_size + added_c]  # PIPE:1507
-        self._check_vae_range()
-        return video.cpu().numpy() if output_type == "np" else video
-
-    def _final_latents(self, latents: torch.Tensor) -> torch.Tensor:
-        """PIPE:999-1000: `latents.to(self.vae.dtype)` and the de-normalisation IN THAT DTYPE (a bf16 VAE module, the LongCat entry's
-        run_longcat_worldforge_single.py:205: constants and both statements in bf16), handed to decode in the module dtype."""
-        vdt = getattr(self.vae, "dtype", torch.float32)
-        z = ops.latent_denorm(ops.cast(latents, vdt), self.vae.config.latents_mean, self.vae.config.latents_std)  # f32 holding vdt values
-        return z if vdt == torch.float32 else ops.cast(z, vdt)
-
-    def _check_vae_range(self):
-        """A VAE call of this job left the fp16 operand range (vae.AutoencoderKLWan.check_range): fail before handing anything back."""
-        if hasattr(self.vae, "check_range"):
-            self.vae.check_range()
+        if enc_in is not None:  # encoded (posterior sample) and normalised
+            cond = self.vae.encode(enc_in).latent_dist.sample(generator).to(dev, torch.float32)
+            latents[:, :, :ncl] = ops.latent_norm(cond, self.vae.config.latents_mean, self.vae.config.latents_std)
+        latents = self._denoise_window(latents, ncl, timesteps, pe, pm, None, step_hook,
+                                       (self.dit.cache_condition_blocks, self.dit.forward_cached_blocks) if use_kv_cache else None)
+        return self._finish(latents, output_type, crop=(added_c, new_frame_size + added_c))  # PIPE:1507
 
     # ---- PIPE:619-1006 ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -393,43 +408,23 @@ class LongCatVideoPipeline:
                      omega_resample: float = 1.0, use_pca_channel_selection: bool = False, static: bool = False,
                      max_replace_threshold: Optional[int] = None, step_hook=None):
         dev, sch = self.device, self.scheduler
-        ssp = self.vae_scale_factor_spatial * 2
-        if height % ssp != 0 or width % ssp != 0:
-            raise ValueError(f"`height and width` have to be divisible by {ssp} but are {height} and {width}.")  # PIPE:199-201
-        if num_frames % self.vae_scale_factor_temporal != 1:
-            num_frames = num_frames // self.vae_scale_factor_temporal * self.vae_scale_factor_temporal + 1  # PIPE:700-704
-        num_frames = max(num_frames, 1)
+        self._check_size(height, width)
+        num_frames = self._snap_frames(num_frames)
         self._guidance_scale = guidance_scale
         do_cfg = self.do_classifier_free_guidance
         dit_dtype = self.dit.dtype
-        pe = prompt_embeds.to(dev, dit_dtype)
-        pm = prompt_attention_mask.to(dev)
-        if do_cfg:
-            if negative_prompt_embeds is None:
-                raise ValueError("classifier-free guidance (guidance_scale > 1) needs the negative prompt embeddings")
-            pe = torch.cat([negative_prompt_embeds.to(dev, dit_dtype), pe], dim=0)  # PIPE:760-762
-            pm = torch.cat([negative_prompt_attention_mask.to(dev), pm], dim=0)
-        # PIPE:764-767
-        sch.set_timesteps(num_inference_steps, sigmas=self.get_timesteps_sigmas(num_inference_steps, use_distill=use_distill), device=dev)
-        timesteps = sch.timesteps
+        pe, pm = prompt_batch(dev, dit_dtype, prompt_embeds, prompt_attention_mask, negative_prompt_embeds,
+                              negative_prompt_attention_mask, do_cfg)
+        timesteps = self._set_timesteps(num_inference_steps, use_distill)
         # PIPE:769-789
-        img = self._preprocess_image(image, height, width).to(dev, dit_dtype)
+        img = sc.preprocess_image(image, height, width).to(dev, dit_dtype)
         latents = self.prepare_latents(img, 1, self.dit.config.in_channels, height, width, num_frames, generator, latents)
         if video_ref is not None and guided:
             video_ref = torch.as_tensor(video_ref).to(dev, torch.float32)  # PIPE:792-801
-        if mask is not None and guided:  # PIPE:803-817
-            mask = torch.from_numpy(mask) if isinstance(mask, np.ndarray) else mask
-            if mask.dim() == 3:
-                mask = mask.unsqueeze(0).unsqueeze(1)
-            elif mask.dim() == 4 and mask.shape[1] != 1:
-                mask = mask[:, 0:1, :, :].unsqueeze(0)
-            elif mask.dim() == 4 and mask.shape[0] == 1:
-                mask = mask.unsqueeze(1)
-            elif mask.dim() == 5 and mask.shape[1] != 1:
-                mask = mask[:, 0:1, :, :, :]
-            mask = mask.to(dev, torch.float32)
-        sch.derivative_history = []
-
+        if mask is not None and guided:
+            mask = sc.guide_mask(mask, dev)  # PIPE:803-817
+        # the condition frame is clean (PIPE:865); under `cfg_split` the two CFG samples run on one group of the job's ranks each
+        forward = self._dit_forward(1, getattr(self, "cfg_split", None) if do_cfg else None)
         for i, t in enumerate(timesteps):
             if step_hook is not None:
                 step_hook(i, "start")
@@ -437,39 +432,10 @@ class LongCatVideoPipeline:
             pred_x0 = None
             scheduler_output = None
             for r in range(resample_steps if (guided and i < resample_round) else 1):
+                sch.set_resample_mode(r > 0)
                 if r > 0:
-                    sch.set_resample_mode(True)
                     sch._step_index -= 1
-                else:
-                    sch.set_resample_mode(False)
-                # PIPE:852-865: the timestep in the DiT dtype, one per latent frame, the condition frame at t = 0
-                ts = t.expand(latents.shape[0]).to(dit_dtype)
-                x_in = ops.cast(latents, dit_dtype)
-                if do_cfg:
-                    x_in = torch.cat([x_in] * 2)
-                    ts = torch.cat([ts] * 2)
-                ts = ts.unsqueeze(-1).repeat(1, x_in.shape[2])
-                ts[:, :1] = 0
-                split = getattr(self, "cfg_split", None) if do_cfg and x_in.shape[0] == 2 else None
-                if split is not None:
-                    # CFG groups x sequence shards (parallel.Comm.split, as pipeline.WanImageToVideoPipeline.cfg_split): the CFG
-                    # batch [negative, positive] of pipeline_longcat_video.py:857-866 is two samples -- group b of the job's ranks runs sample
-                    # b as ONE forward, one all-gather over the whole job hands every rank both velocities (slots 0 and P / 2)
-                    world_comm, b = split
-                    own = self.dit(hidden_states=x_in[b:b + 1], timestep=ts[b:b + 1], encoder_hidden_states=pe[b:b + 1],
-                                   encoder_attention_mask=pm[b:b + 1], num_cond_latents=1).contiguous()
-                    both = torch.empty((world_comm.world,) + tuple(own.shape), dtype=own.dtype, device=own.device)
-                    world_comm.all_gather(both, own)
-                    noise_pred = torch.cat([both[0], both[world_comm.world // 2]])
-                else:
-                    noise_pred = self.dit(hidden_states=x_in, timestep=ts, encoder_hidden_states=pe, encoder_attention_mask=pm,
-                                          num_cond_latents=1)
-                if do_cfg:
-                    # CFG-zero (PIPE:875-885) and the sign flip of PIPE:888 in one launch per sample
-                    u, c = noise_pred.chunk(2)
-                    noise_pred = torch.stack([ops.cfg_zero(c[b], u[b], guidance_scale, negate=True) for b in range(c.shape[0])])
-                else:
-                    noise_pred = -noise_pred
+                noise_pred = self._velocity(forward, latents, t, pe, pm, guidance_scale if do_cfg else None, 1)
                 scheduler_output = sch.step(
                     noise_pred[:, :, 1:], t, latents[:, :, 1:], video_ref=video_ref, mask=mask, guided=guided and i < guide_steps,
                     resampling=r > 0, vae=self.vae, use_pca_channel_selection=use_pca_channel_selection, static=static,
@@ -480,26 +446,23 @@ class LongCatVideoPipeline:
                 if i >= resample_round:
                     break
                 if r < resample_steps - 1 and pred_x0 is not None:
-                    noise = self._randn(tuple(pred_x0.shape), generator).to(pred_x0.dtype)
+                    noise = sc.randn(tuple(pred_x0.shape), generator, dev).to(pred_x0.dtype)  # PIPE:925
                     latents[:, :, 1:] = sch.add_noise(pred_x0, noise, t.expand(pred_x0.shape[0]), use_resample_sigma=False)
             sch.set_resample_mode(False)
             if i < resample_round and len(sch.derivative_history) > 1 and guided:
-                # DSG (PIPE:945-976): cosine-corrected extrapolation from the first to the last prediction of this step
-                current_omega = omega_resample if i >= guide_steps else omega
-                better = ops.dsg(sch.derivative_history[-1].contiguous(), sch.derivative_history[0].contiguous(), current_omega)
-                sch._step_index -= 1
-                out = sch.step(better, t, latents[:, :, 1:], guided=False, resampling=False, vae=self.vae, sample_full=latents,
-                               use_distill=use_distill, return_dict=True)
-                latents[:, :, 1:] = out.prev_sample
+                latents[:, :, 1:] = self._dsg_step(latents, t, omega_resample if i >= guide_steps else omega, use_distill)
             elif scheduler_output is not None:
                 latents[:, :, 1:] = scheduler_output.prev_sample
             if step_hook is not None:
                 step_hook(i, "end")
+        return self._finish(latents, output_type)
 
-        if output_type == "latent":
-            self._check_vae_range()
-            return latents
-        video = self.vae.decode(self._final_latents(latents), return_dict=False)[0]
-        video = torch.stack([ops.postprocess_video(v) for v in video])  # [B,F,H,W,C] in [0,1]
-        self._check_vae_range()
-        return video.cpu().numpy() if output_type == "np" else video
+    def _dsg_step(self, latents, t, omega, use_distill):
+        """DSG (PIPE:945-976): cosine-corrected extrapolation from the first to the last velocity of this step's rounds, and the step
+        taken again along it.  -> the stepped frames 1.."""
+        sch = self.scheduler
+        better = ops.dsg(sch.derivative_history[-1].contiguous(), sch.derivative_history[0].contiguous(), omega)
+        sch._step_index -= 1
+        out = sch.step(better, t, latents[:, :, 1:], guided=False, resampling=False, vae=self.vae, sample_full=latents,
+                       use_distill=use_distill, return_dict=True)
+        return out.prev_sample

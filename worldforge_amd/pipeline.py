@@ -13,10 +13,10 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, List, Optional, Union
 
-import numpy as np
 import torch
 
 from . import ops, trace
+from . import sampler_common as sc
 
 
 @dataclass
@@ -58,19 +58,6 @@ class WanImageToVideoPipeline:
         if image_embeds is None:
             raise ValueError("Must provide `image_embeds` (CLIP penultimate hidden states [B,257,1280])")
 
-    def _preprocess_image(self, image, height, width) -> torch.Tensor:
-        """diffusers VideoProcessor.preprocess: -> [1,3,H,W] fp32 in [-1,1] on the device."""
-        if isinstance(image, torch.Tensor):
-            t = image if image.dim() == 4 else image.unsqueeze(0)
-            t = t.to(torch.float32)
-        else:
-            if image.size != (width, height):
-                image = image.resize((width, height))
-            t = torch.from_numpy(np.array(image).astype(np.float32) / 255.0).permute(2, 0, 1).unsqueeze(0)
-        if t.shape[-2:] != (height, width):
-            raise ValueError(f"image tensor is {tuple(t.shape[-2:])}, expected {(height, width)}")
-        return (2.0 * t - 1.0).to(self.device)
-
     # ---- PIPE:301-362 ---------------------------------------------------------------------------------------
     def prepare_latents(self, image: torch.Tensor, batch_size: int, num_channels_latents: int, height: int, width: int,
                         num_frames: int, generator=None, latents: Optional[torch.Tensor] = None):
@@ -79,11 +66,7 @@ class WanImageToVideoPipeline:
         h, w = height // ss, width // ss
         shape = (batch_size, num_channels_latents, T, h, w)
         if latents is None:
-            # diffusers randn_tensor: CPU generator -> draw on CPU, then move (RNG parity with the reference)
-            if generator is not None and generator.device.type == "cpu":
-                latents = torch.randn(shape, generator=generator, dtype=torch.float32).to(self.device)
-            else:
-                latents = torch.randn(shape, generator=generator, dtype=torch.float32, device=self.device)
+            latents = sc.randn(shape, generator, self.device, torch.float32)  # PIPE:323
         else:
             latents = latents.to(device=self.device, dtype=torch.float32)
         video_condition = torch.zeros((image.shape[0], image.shape[1], num_frames, height, width), dtype=torch.float32,
@@ -97,6 +80,97 @@ class WanImageToVideoPipeline:
         mask_lat = torch.zeros((batch_size, ts, T, h, w), dtype=torch.float32, device=self.device)
         mask_lat[:, :, 0] = 1.0
         return latents, torch.cat([mask_lat, latent_condition], dim=1)
+
+    def _prepare_embeds(self, prompt_embeds, negative_prompt_embeds, image_embeds):
+        """-> (prompt, negative prompt or None, image) embeddings on the device in the transformer dtype, the image's once per prompt."""
+        device, dtype = self.device, self.transformer.dtype
+        prompt_embeds = prompt_embeds.to(device=device, dtype=dtype)
+        if self.do_classifier_free_guidance:
+            if negative_prompt_embeds is None:
+                raise ValueError("classifier-free guidance needs `negative_prompt_embeds`")
+            negative_prompt_embeds = negative_prompt_embeds.to(device=device, dtype=dtype)
+        image_embeds = image_embeds.to(device=device, dtype=dtype)
+        if image_embeds.shape[0] != prompt_embeds.shape[0]:
+            image_embeds = image_embeds.repeat(prompt_embeds.shape[0], 1, 1)
+        return prompt_embeds, negative_prompt_embeds, image_embeds
+
+    # ---- PIPE:593-614 ---------------------------------------------------------------------------------------
+    def _velocity(self, x, timestep, prompt_embeds, negative_prompt_embeds, image_embeds, attention_kwargs):
+        """The transformer's velocity for model input x; under CFG, both branches by one of three routes, combined."""
+        def forward(text_embeds):
+            return self.transformer(hidden_states=x, timestep=timestep, encoder_hidden_states=text_embeds,
+                                    encoder_hidden_states_image=image_embeds, attention_kwargs=attention_kwargs, return_dict=False)[0]
+
+        if not self.do_classifier_free_guidance:
+            return forward(prompt_embeds)
+        split = getattr(self, "cfg_split", None)
+        pair = getattr(self.transformer, "forward_cfg_pair", None)
+        if split is not None:
+            # group 0 runs the positive-prompt forward, group 1 the negative one
+            cond, uncond = sc.cfg_groups_exchange(split, lambda branch: forward(prompt_embeds if branch == 0 else negative_prompt_embeds))
+        elif pair is not None:
+            # same two calls as below, advanced in lock-step so that under sequence parallelism each branch's K / V
+            # exchange overlaps the other branch's compute (dit.forward_tokens_pair); identical results
+            cond, uncond = pair(hidden_states=x, timestep=timestep, encoder_hidden_states=prompt_embeds,
+                                negative_encoder_hidden_states=negative_prompt_embeds, encoder_hidden_states_image=image_embeds)
+        else:
+            cond, uncond = forward(prompt_embeds), forward(negative_prompt_embeds)
+        return ops.cfg_combine(cond, uncond, self.guidance_scale)
+
+    @staticmethod
+    def _rewind(sch):
+        """Take back the step counter and the order warm-up of the UniPC step just made: the same step is taken again."""
+        sch._step_index -= 1
+        if sch.lower_order_nums > 0 and sch.last_lower_order_nums < sch.config.solver_order:
+            sch.lower_order_nums -= 1
+
+    # ---- PIPE:569-660 ---------------------------------------------------------------------------------------
+    def _step_rounds(self, i, t, latents, condition, embeds, attention_kwargs, generator, resample_steps, resample_round, step_kw):
+        """Step i's rounds: the velocity and the scheduler's step; then, before step resample_round, resample_steps - 1 times over, the
+        predicted clean sample re-noised to this step's level and the same step taken again from there.  step_kw: what sch.step is
+        given alike in every round.  -> (the latents the last round started from, its scheduler output)."""
+        sch, tr = self.scheduler, self.tracer
+        scheduler_output = None
+        for r in range(resample_steps):
+            sch.set_resample_mode(r > 0)
+            if r > 0:
+                self._rewind(sch)
+                sch.this_order = sch.last_this_order
+            timestep_for_transformer = (sch.get_resample_timestep(i) if r > 0 else t).expand(latents.shape[0])
+            latent_model_input = self._model_input(latents, condition, self.transformer.dtype)
+            with tr.range("dit_cfg", step=i, round=r):
+                noise_pred = self._velocity(latent_model_input, timestep_for_transformer, *embeds, attention_kwargs)
+                if self.do_classifier_free_guidance and r < 1:
+                    sch.derivative_history.append(noise_pred)
+            with tr.range("scheduler_step", step=i, round=r):
+                scheduler_output = sch.step(noise_pred, t, latents, resampling=r > 0, return_dict=True, current_step=i,
+                                            resample_count=resample_steps, is_resample_round=i < resample_round, **step_kw)
+            pred_original_sample = scheduler_output.pred_x0
+            if i >= resample_round:
+                break
+            if r < resample_steps - 1 and pred_original_sample is not None:
+                noise = sc.randn(pred_original_sample.shape, generator, self.device)  # PIPE:644
+                with tr.range("renoise", step=i, round=r):
+                    latents = sch.add_noise(pred_original_sample, noise, sch.get_resample_timestep(i), r,
+                                            use_resample_sigma=True)
+        return latents, scheduler_output
+
+    # ---- PIPE:664-708 ---------------------------------------------------------------------------------------
+    def _dsg_step(self, latents, omega, step):
+        """DSG: extrapolate from the first to the last velocity of this step's rounds and take the step again with the result, the
+        UniPC state put back by hand; the latents come out in the transformer dtype (PIPE:708)."""
+        sch = self.scheduler
+        with self.tracer.range("dsg", step=step):
+            better = ops.dsg(sch.derivative_history[-1], sch.derivative_history[0], omega)
+        self._rewind(sch)
+        converted = sch.convert_model_output(better, sample=latents)
+        sch.last_sample = latents
+        sch.model_outputs[-1] = converted
+        latents = sch.multistep_uni_p_bh_update(model_output=better, sample=latents, order=sch.this_order)
+        sch._step_index += 1
+        if 0 <= sch.lower_order_nums < sch.config.solver_order:
+            sch.lower_order_nums += 1
+        return ops.cast(latents, self.transformer.dtype)
 
     # ---- PIPE:388-753 ---------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -121,22 +195,12 @@ class WanImageToVideoPipeline:
             num_frames = num_frames // ts * ts + 1  # PIPE:475-477
         num_frames = max(num_frames, 1)
         self._guidance_scale = guidance_scale
-        device = self.device
-        sch = self.scheduler
+        device, sch = self.device, self.scheduler
         batch_size = prompt_embeds.shape[0]
-        transformer_dtype = self.transformer.dtype
-        prompt_embeds = prompt_embeds.to(device=device, dtype=transformer_dtype)
-        if self.do_classifier_free_guidance:
-            if negative_prompt_embeds is None:
-                raise ValueError("classifier-free guidance needs `negative_prompt_embeds`")
-            negative_prompt_embeds = negative_prompt_embeds.to(device=device, dtype=transformer_dtype)
-        image_embeds = image_embeds.to(device=device, dtype=transformer_dtype)
-        if image_embeds.shape[0] != batch_size:
-            image_embeds = image_embeds.repeat(batch_size, 1, 1)
-
+        embeds = self._prepare_embeds(prompt_embeds, negative_prompt_embeds, image_embeds)
         sch.set_timesteps(num_inference_steps, device=device)
         timesteps = sch.timesteps
-        img = self._preprocess_image(image, height, width)
+        img = sc.preprocess_image(image, height, width).to(device)
         latents, condition = self.prepare_latents(img, batch_size * num_videos_per_prompt, self.vae.config.z_dim, height,
                                                   width, num_frames, generator, latents)
         if video_ref is not None and guided:
@@ -144,17 +208,7 @@ class WanImageToVideoPipeline:
                 video_ref = torch.tensor(video_ref)
             video_ref = video_ref.to(dtype=torch.float32).to(device=device)
         if mask is not None and guided:
-            if isinstance(mask, np.ndarray):
-                mask = torch.from_numpy(mask)
-            if mask.dim() == 3:
-                mask = mask.unsqueeze(0).unsqueeze(1)
-            elif mask.dim() == 4 and mask.shape[1] != 1:
-                mask = mask[:, 0:1, :, :].unsqueeze(0)
-            elif mask.dim() == 4 and mask.shape[0] == 1:
-                mask = mask.unsqueeze(1)
-            elif mask.dim() == 5 and mask.shape[1] != 1:
-                mask = mask[:, 0:1, :, :, :]
-            mask = mask.to(device=device, dtype=torch.float32).contiguous()  # fp64 -> fp32 is what SCHED:1374 does per call
+            mask = sc.guide_mask(mask, device).contiguous()  # fp64 -> fp32 is what SCHED:1374 does per call
         if not hasattr(sch, "derivative_history"):
             sch.derivative_history = []
 
@@ -173,94 +227,12 @@ class WanImageToVideoPipeline:
             if step_hook is not None:
                 step_hook(i, "begin")
             sch.derivative_history = []
-            pred_original_sample = None
-            scheduler_output = None
-            for r in range(resample_steps):
-                if r > 0:
-                    sch.set_resample_mode(True)
-                    timestep_for_transformer = sch.get_resample_timestep(i).expand(latents.shape[0])
-                else:
-                    sch.set_resample_mode(False)
-                    timestep_for_transformer = t.expand(latents.shape[0])
-                if r > 0:
-                    sch._step_index -= 1
-                    if sch.lower_order_nums > 0 and sch.last_lower_order_nums < sch.config.solver_order:
-                        sch.lower_order_nums -= 1
-                    sch.this_order = sch.last_this_order
-                latent_model_input = self._model_input(latents, condition, transformer_dtype)
-                with tr.range("dit_cfg", step=i, round=r):
-                    pair = getattr(self.transformer, "forward_cfg_pair", None) if self.do_classifier_free_guidance else None
-                    split = getattr(self, "cfg_split", None) if self.do_classifier_free_guidance else None
-                    if split is not None:
-                        # CFG groups x sequence shards (SURVEY 8e "P = 8 = 2 x 4"; parallel.Comm.split): the ranks of group 0 run the
-                        # positive-prompt forward, those of group 1 the negative one -- ONE forward per rank and evaluation on a token
-                        # shard twice as long, half the K / V^T exchange -- and every rank then takes both velocities from one small
-                        # all-gather over the whole job (a rank's slot holds its group's full tensor: [P, ...] -> slots 0 and P / 2)
-                        world_comm, branch = split
-                        own = self.transformer(hidden_states=latent_model_input, timestep=timestep_for_transformer,
-                                               encoder_hidden_states=prompt_embeds if branch == 0 else negative_prompt_embeds,
-                                               encoder_hidden_states_image=image_embeds, attention_kwargs=attention_kwargs,
-                                               return_dict=False)[0].contiguous()
-                        both = torch.empty((world_comm.world,) + tuple(own.shape), dtype=own.dtype, device=own.device)
-                        world_comm.all_gather(both, own)
-                        noise_pred, noise_uncond = both[0], both[world_comm.world // 2]
-                    elif pair is not None:
-                        # same two calls as below, advanced in lock-step so that under sequence parallelism each branch's K / V
-                        # exchange overlaps the other branch's compute (dit.forward_tokens_pair); identical results
-                        noise_pred, noise_uncond = pair(hidden_states=latent_model_input, timestep=timestep_for_transformer,
-                                                        encoder_hidden_states=prompt_embeds,
-                                                        negative_encoder_hidden_states=negative_prompt_embeds,
-                                                        encoder_hidden_states_image=image_embeds)
-                    else:
-                        noise_pred = self.transformer(hidden_states=latent_model_input, timestep=timestep_for_transformer,
-                                                      encoder_hidden_states=prompt_embeds,
-                                                      encoder_hidden_states_image=image_embeds, attention_kwargs=attention_kwargs,
-                                                      return_dict=False)[0]
-                        if self.do_classifier_free_guidance:
-                            noise_uncond = self.transformer(hidden_states=latent_model_input, timestep=timestep_for_transformer,
-                                                            encoder_hidden_states=negative_prompt_embeds,
-                                                            encoder_hidden_states_image=image_embeds,
-                                                            attention_kwargs=attention_kwargs, return_dict=False)[0]
-                    if self.do_classifier_free_guidance:
-                        noise_pred = ops.cfg_combine(noise_pred, noise_uncond, guidance_scale)
-                        if r < 1:
-                            sch.derivative_history.append(noise_pred)
-                with tr.range("scheduler_step", step=i, round=r):
-                    scheduler_output = sch.step(noise_pred, t, latents, mask=mask,
-                                                guided=guided and i < guide_steps and r < resample_steps,
-                                                video_latents=video_ref, vae=self.vae, resampling=r > 0, return_dict=True,
-                                                current_step=i, resample_count=resample_steps,
-                                                is_resample_round=i < resample_round,
-                                                use_pca_channel_selection=use_pca_channel_selection, static=static)
-                pred_original_sample = scheduler_output.pred_x0
-                if i >= resample_round:
-                    break
-                if r < resample_steps - 1 and pred_original_sample is not None:
-                    if generator is not None:
-                        noise = torch.randn(pred_original_sample.shape, generator=generator).to(device=device)
-                    else:
-                        noise = torch.randn(pred_original_sample.shape, device=device)
-                    with tr.range("renoise", step=i, round=r):
-                        latents = sch.add_noise(pred_original_sample, noise, sch.get_resample_timestep(i), r,
-                                                use_resample_sigma=True)
+            step_kw = dict(mask=mask, guided=guided and i < guide_steps, video_latents=video_ref, vae=self.vae,
+                           use_pca_channel_selection=use_pca_channel_selection, static=static)
+            latents, scheduler_output = self._step_rounds(i, t, latents, condition, embeds, attention_kwargs, generator,
+                                                          resample_steps, resample_round, step_kw)
             if len(sch.derivative_history) > 1:
-                noise_pred_good = sch.derivative_history[-1]
-                noise_pred_worse = sch.derivative_history[0]
-                if i >= guide_steps:
-                    omega = omega_resample
-                with tr.range("dsg", step=i):
-                    noise_pred_better = ops.dsg(noise_pred_good, noise_pred_worse, omega)
-                sch._step_index -= 1
-                if sch.lower_order_nums > 0 and sch.last_lower_order_nums < sch.config.solver_order:
-                    sch.lower_order_nums -= 1
-                noise_pred_convert = sch.convert_model_output(noise_pred_better, sample=latents)
-                sch.last_sample = latents
-                sch.model_outputs[-1] = noise_pred_convert
-                latents = sch.multistep_uni_p_bh_update(model_output=noise_pred_better, sample=latents, order=sch.this_order)
-                sch._step_index += 1
-                if 0 <= sch.lower_order_nums < sch.config.solver_order:
-                    sch.lower_order_nums += 1
-                latents = ops.cast(latents, transformer_dtype)
+                latents = self._dsg_step(latents, omega_resample if i >= guide_steps else omega, i)
             else:
                 latents = scheduler_output.prev_sample
             sch.set_resample_mode(False)
@@ -271,18 +243,7 @@ class WanImageToVideoPipeline:
             if step_hook is not None:
                 step_hook(i, "end")
 
-        if output_type == "latent":
-            video = latents
-        else:
-            z = ops.latent_denorm(ops.cast(latents, torch.float32), self.vae.config.latents_mean,
-                                  self.vae.config.latents_std)
-            with tr.range("final_decode"):
-                video = self.vae.decode(z, return_dict=False)[0]
-                video = torch.stack([ops.postprocess_video(v) for v in video])  # [B,F,H,W,C]
-            if output_type == "np":
-                video = video.cpu().numpy()
-        if hasattr(self.vae, "check_range"):
-            self.vae.check_range()   # a VAE call of this job left the fp16 range: fail before handing anything back
+        video = sc.decode_tail(self.vae, latents, output_type, self._vae_input, tracer=tr)
         if tr.enabled:
             self.timing = tr.summary()
             if getattr(tr, "path", None):
@@ -295,3 +256,8 @@ class WanImageToVideoPipeline:
         """PIPE:590: cat([latents, condition], 1).to(transformer_dtype)."""
         x = torch.cat([latents.to(torch.float32), condition], dim=1)
         return ops.cast(x, dtype)
+
+    def _vae_input(self, latents):
+        """PIPE:733-742: the final latents in fp32, de-normalised."""
+        return ops.latent_denorm(ops.cast(latents, torch.float32), self.vae.config.latents_mean, self.vae.config.latents_std)
+
