@@ -423,6 +423,32 @@ int wf_clip_attn_fwd(const float* Q, const float* K, const float* V, int ldqkv, 
  * [G * G][3 * p * p], G = S / p, row py * G + px, column c * p * p + ph * p + pw (the flattening order of the conv weight): a copy, exact. */
 int wf_clip_patch_rows(const float* pixels, float* rows, int S, int p, void* stream);
 
+/* ---- VGGT front-end (csrc/vit.hip; vggt/models/aggregator.py, vggt/layers/attention.py, rope.py; worldforge_amd/vggt.py is the host): the
+ *      DINOv2 backbone and the frame / global blocks run on wf_gemm_bf16 with an fp32 residual stream (what bf16 autocast leaves). ---- */
+/* Attention.forward's F.scaled_dot_product_attention without a mask (attention.py:50-72): O = softmax_j(scale * q_i . k_j) V for nseq
+ * independent sequences of L tokens, H heads of 64 channels, bf16.  Q, K, V are three column slices of one stacked [nseq * L, ldqkv] buffer
+ * (head h at columns h * 64; ldqkv % 8 == 0, 16-byte aligned), O bf16 [nseq * L, ldo] (ldo % 4 == 0, 8-byte aligned); sequence s is rows
+ * s * L .. s * L + L - 1 and no row of another sequence is read.  Any L >= 1: the keys stream through LDS in 64-key tiles with an online
+ * softmax, the last tile masked inside the kernel.  Scores, running maximum, p and the row sum (of the un-rounded p) are fp32, P is rounded
+ * once to bf16, both products are bf16 MFMA with fp32 accumulation, one rounding of the output.  No atomics: two calls give the same bits.
+ * WF_EINVAL before any device work unless 1 <= nseq, H <= 65535, L >= 1, nseq * L < 2^31, scale positive and finite. */
+int wf_vit_attn_fwd(const void* Q, const void* K, const void* V, int ldqkv, void* O, int ldo, int nseq, int H, int L, float scale,
+                    void* stream);
+/* q_norm / k_norm and the 2D RoPE (attention.py:54-58, rope.py:133-188), in place on the q and k slices of the stacked bf16 buffer
+ * [nseq * L, ldqkv] (head h at columns h * 64; the v slice is not touched).  Per row and head: LayerNorm over the 64 channels (f32 weight /
+ * bias [64] per slice, eps), then channels 0..31 rotated by the token's y position and 32..63 by its x position, each half pairing
+ * (i, i + 16) with 16 frequencies: out[i] = x[i] cos - x[i+16] sin, out[i+16] = x[i+16] cos + x[i] sin.  cos / sin f32 [max_pos + 1][16],
+ * pos int32 [L][2] = (y, x) of the token inside its sequence (aggregator.py:223-228: special tokens (0, 0) = the identity, patch (y, x)
+ * carries (y + 1, x + 1)); a position outside 0..max_pos is clamped.  fp32 arithmetic, one rounding; q is multiplied by out_scale in front
+ * of the rounding (1 = none).  All four norm pointers NULL: no LayerNorm; cos, sin, pos NULL: no rotation. */
+int wf_vit_qk_norm_rope(void* Q, void* K, int ldqkv, const float* q_weight, const float* q_bias, const float* k_weight,
+                        const float* k_bias, float eps, const float* cos_tab, const float* sin_tab, int max_pos, const int* pos,
+                        int nseq, int L, int H, float out_scale, void* stream);
+/* aggregator.py:201 + PatchEmbed's Conv2d with kernel = stride = 14 as a GEMM operand: images f32 [n][3][H][W] in [0, 1] -> rows bf16
+ * [n * (H/14) * (W/14)][592] = rn_bf16((x - mean_c) / std_c) (ResNet statistics, fp32) at column c * 196 + ph * 14 + pw; columns 588..591
+ * are zero (wf_gemm_bf16 needs K % 8 == 0: the conv weight is stored [C][592] with the same zero columns).  H, W multiples of 14. */
+int wf_vit_patch_rows(const float* images, void* rows, int n, int H, int W, void* stream);
+
 /* ---- 3D causal VAE (wan/modules/vae.py; the in-tree statement of diffusers' AutoencoderKLWan), channels-last ----------- */
 /* CausalConv3d / Conv2d as implicit GEMM on MFMA (vae.py:17-36, 76-96, 186-220).  in bf16 [Ti,Hi,Wi,Cin] (Cin % 32 == 0),
  * w bf16 [Cout][kt*kh*kw][Cin], bias f32; out (f32 and/or bf16) [To,Ho,Wo,Cout] (+ resid f32 of the same shape).

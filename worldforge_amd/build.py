@@ -38,6 +38,7 @@ SOURCES = {
     "longcat_ops.hip": ["-ffp-contract=off"],
     "t5.hip": [],
     "clip.hip": [],
+    "vit.hip": [],
     "vae_ops.hip": [],
     "conv.hip": [],
     "warp.hip": ["-ffp-contract=off"],

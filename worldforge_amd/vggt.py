@@ -1,0 +1,558 @@
+"""VGGT's aggregator and camera head on this engine's own kernels: images in; aggregated tokens, `pose_enc`, extrinsics, intrinsics out.
+
+What the reference runs as `model.aggregator(images)` under bf16 autocast, then `model.camera_head(tokens)` in fp32 (vggt/run_warp.py:212-234;
+AGG = vggt/models/aggregator.py, ATT = vggt/layers/attention.py, ROPE = vggt/layers/rope.py, DINO = vggt/layers/vision_transformer.py,
+CAM = vggt/heads/camera_head.py).  The aggregator's linears are bf16 MFMA (wf_gemm_bf16, weights rounded once at load: what autocast does
+per call) on an fp32 residual stream; LayerNorms, LayerScale, tokens and the position table are fp32.  The camera head is fp32 throughout.
+
+    rows = wf_vit_patch_rows(images)                              (x - mean) / std in fp32, bf16 [n P, 592]
+    DINOv2 (DINO:214-271), per frame T = 5 + P tokens:
+    x    = [cls + pos_0; registers; pos' + wf_gemm_bf16(rows, proj)]     pos' = position table, bicubic + antialias to the patch grid (cached)
+    per block:  n = wf_ln_modulate(x) -> bf16;  qkv = wf_gemm_bf16(n);  a = wf_vit_attn_fwd(qkv, nseq = S, L = T)
+                x += ls1 * wf_gemm_bf16(a, proj)   WF_EPI_RESID;   h = wf_gemm_bf16(n2, fc1) f32 -> wf_act GELU-erf -> bf16;  x += ls2 * fc2
+    patch tokens = rows 5.. of wf_ln_modulate(x, norm)
+    aggregator (AGG:184-258): tokens = [camera_token[i]; register_token[i]; patch tokens], i = 0 for frame 0 and 1 for the others
+    per depth: a frame block (nseq = S, L = T) then a global block (nseq = 1, L = S T): the same block with wf_vit_qk_norm_rope
+               (per-head LayerNorm on q and k + 2D RoPE) in front of the attention; kept layers = cat(frame out, global out) [S, T, 2 C]
+    camera head (CAM:73-141) on the last layer's camera tokens [S, 2 C]: wf_gemm_f32, wf_clip_attn_fwd (D = 128, L = S), wf_ln_modulate,
+    the AdaLN modulate / gate and the activations as torch ops on [S, 2 C].
+
+Not built: the depth / point / track heads (the DPT depth head is the next step: it consumes exactly the four kept layers), `mode="pad"`
+of the preprocessing, images of mixed shapes.
+"""
+from __future__ import annotations
+
+import json
+import os
+import warnings
+from dataclasses import dataclass
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+WF_F32, WF_BF16 = 0, 1
+EPI_BF16, EPI_F32, EPI_RESID, EPI_F32_ACC, EPI_F32_GELU = 0, 2, 3, 4, 5
+PATCH_K = 592                 # 3 * 14 * 14 = 588 padded to a multiple of 8 (wf_vit_patch_rows)
+MAX_FRAMES = 1024             # wf_clip_attn_fwd over the camera tokens
+IGNORED = ("depth_head.", "point_head.", "track_head.", "aggregator.patch_embed.mask_token")
+KEEP = (4, 11, 17, 23)
+
+
+@dataclass(frozen=True)
+class VGGTConfig:
+    img_size: int = 518
+    patch_size: int = 14
+    embed_dim: int = 1024
+    depth: int = 24
+    num_heads: int = 16
+    mlp_ratio: float = 4.0
+    num_register_tokens: int = 4
+    rope_freq: float = 100.0
+    init_values: float = 0.01
+    qk_norm: bool = True
+    aa_order: Tuple[str, ...] = ("frame", "global")
+    aa_block_size: int = 1
+    patch_embed: str = "dinov2_vitl14_reg"
+    dino_depth: int = 24
+    dino_num_heads: int = 16
+    dino_eps: float = 1e-6
+    dino_init_values: float = 1.0
+    camera_trunk_depth: int = 4
+    camera_num_heads: int = 16
+    camera_iterations: int = 4
+
+    @property
+    def patch_start_idx(self) -> int:
+        return 1 + self.num_register_tokens
+
+    @property
+    def hidden(self) -> int:
+        return int(self.embed_dim * self.mlp_ratio)
+
+    @property
+    def pos_grid(self) -> int:
+        return self.img_size // self.patch_size
+
+    @property
+    def camera_dim(self) -> int:
+        return 2 * self.embed_dim
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "VGGTConfig":
+        d = dict(d)
+        if "aa_order" in d:
+            d["aa_order"] = tuple(d["aa_order"])
+        cfg = cls(**{k: d[k] for k in cls.__dataclass_fields__ if k in d})
+        if cfg.patch_size != 14:
+            raise NotImplementedError(f"patch_size {cfg.patch_size}: wf_vit_patch_rows is built for 14")
+        if cfg.embed_dim % cfg.num_heads or cfg.embed_dim // cfg.num_heads != 64:
+            raise NotImplementedError(f"aggregator head width {cfg.embed_dim / cfg.num_heads:g}: wf_vit_attn_fwd is built for 64")
+        if cfg.embed_dim % cfg.dino_num_heads or cfg.embed_dim // cfg.dino_num_heads != 64:
+            raise NotImplementedError(f"DINOv2 head width {cfg.embed_dim / cfg.dino_num_heads:g}: wf_vit_attn_fwd is built for 64")
+        if tuple(cfg.aa_order) != ("frame", "global"):
+            raise NotImplementedError(f"aa_order {list(cfg.aa_order)}: built is ['frame', 'global']")
+        if cfg.aa_block_size != 1:
+            raise NotImplementedError(f"aa_block_size {cfg.aa_block_size}: built is 1")
+        if not cfg.rope_freq > 0:
+            raise NotImplementedError(f"rope_freq {cfg.rope_freq}: the blocks are built with the 2D RoPE")
+        if not cfg.qk_norm:
+            raise NotImplementedError("qk_norm off: the frame and global blocks are built with q_norm / k_norm")
+        if not cfg.patch_embed.startswith("dinov2"):
+            raise NotImplementedError(f"patch_embed {cfg.patch_embed!r}: built is the DINOv2 ViT")
+        if cfg.camera_dim % cfg.camera_num_heads or not 8 <= cfg.camera_dim // cfg.camera_num_heads <= 128 or (cfg.camera_dim // cfg.camera_num_heads) % 8:
+            raise NotImplementedError("camera trunk head width: wf_clip_attn_fwd takes multiples of 8 in 8..128")
+        if min(cfg.depth, cfg.dino_depth, cfg.camera_trunk_depth, cfg.num_register_tokens, cfg.img_size) < 1 or cfg.img_size % 14:
+            raise ValueError("depths, register tokens and img_size must be positive, img_size a multiple of 14")
+        return cfg
+
+    @classmethod
+    def from_json(cls, path: str) -> "VGGTConfig":
+        with open(path) as f:
+            return cls.from_dict(json.load(f))
+
+
+def _block_keys(prefix: str, C: int, F: int, qk_norm: bool) -> Dict[str, Tuple[int, ...]]:
+    out = {}
+    for n in ("norm1", "norm2"):
+        out[f"{prefix}{n}.weight"], out[f"{prefix}{n}.bias"] = (C,), (C,)
+    out[f"{prefix}attn.qkv.weight"], out[f"{prefix}attn.qkv.bias"] = (3 * C, C), (3 * C,)
+    out[f"{prefix}attn.proj.weight"], out[f"{prefix}attn.proj.bias"] = (C, C), (C,)
+    if qk_norm:
+        for n in ("q_norm", "k_norm"):
+            out[f"{prefix}attn.{n}.weight"], out[f"{prefix}attn.{n}.bias"] = (64,), (64,)
+    out[f"{prefix}ls1.gamma"], out[f"{prefix}ls2.gamma"] = (C,), (C,)
+    out[f"{prefix}mlp.fc1.weight"], out[f"{prefix}mlp.fc1.bias"] = (F, C), (F,)
+    out[f"{prefix}mlp.fc2.weight"], out[f"{prefix}mlp.fc2.bias"] = (C, F), (C,)
+    return out
+
+
+def expected_state_dict(cfg: VGGTConfig) -> Dict[str, Tuple[int, ...]]:
+    """{key of the reference's VGGT module: shape} of everything this engine uploads: `aggregator.*` (without the DINOv2 mask token) and
+    `camera_head.*`."""
+    C, F, R, D = cfg.embed_dim, cfg.hidden, cfg.num_register_tokens, cfg.camera_dim
+    out: Dict[str, Tuple[int, ...]] = {"aggregator.camera_token": (1, 2, 1, C), "aggregator.register_token": (1, 2, R, C)}
+    pe = "aggregator.patch_embed."
+    out.update({pe + "cls_token": (1, 1, C), pe + "pos_embed": (1, 1 + cfg.pos_grid ** 2, C), pe + "register_tokens": (1, R, C),
+                pe + "patch_embed.proj.weight": (C, 3, 14, 14), pe + "patch_embed.proj.bias": (C,), pe + "norm.weight": (C,), pe + "norm.bias": (C,)})
+    for i in range(cfg.dino_depth):
+        out.update(_block_keys(f"{pe}blocks.{i}.", C, F, False))
+    for i in range(cfg.depth):
+        out.update(_block_keys(f"aggregator.frame_blocks.{i}.", C, F, True))
+        out.update(_block_keys(f"aggregator.global_blocks.{i}.", C, F, True))
+    ch = "camera_head."
+    for i in range(cfg.camera_trunk_depth):
+        out.update(_block_keys(f"{ch}trunk.{i}.", D, 4 * D, False))
+    for n in ("token_norm", "trunk_norm"):
+        out[f"{ch}{n}.weight"], out[f"{ch}{n}.bias"] = (D,), (D,)
+    out.update({ch + "empty_pose_tokens": (1, 1, 9), ch + "embed_pose.weight": (D, 9), ch + "embed_pose.bias": (D,),
+                ch + "poseLN_modulation.1.weight": (3 * D, D), ch + "poseLN_modulation.1.bias": (3 * D,),
+                ch + "pose_branch.fc1.weight": (D // 2, D), ch + "pose_branch.fc1.bias": (D // 2,),
+                ch + "pose_branch.fc2.weight": (9, D // 2), ch + "pose_branch.fc2.bias": (9,)})
+    return out
+
+
+def consumed_header(found: Dict[str, dict], where: str = "checkpoint") -> Dict[str, dict]:
+    """The entries this engine uploads; the heads that are not built and the DINOv2 mask token are dropped with ONE warning."""
+    keep = {k: v for k, v in found.items() if not k.startswith(IGNORED)}
+    if len(keep) != len(found):
+        groups = sorted({g for g in IGNORED for k in found if k.startswith(g)})
+        warnings.warn(f"{where}: {len(found) - len(keep)} tensors of {', '.join(groups)} are not consumed (heads not built here) and are ignored",
+                      UserWarning, stacklevel=3)
+    return keep
+
+
+def _raise_on(keep: Dict[str, dict], cfg: VGGTConfig, where: str):
+    from .checkpoint import compare_header
+    missing, unexpected, wrong = compare_header(keep, expected_state_dict(cfg))
+    if missing:
+        raise KeyError(f"{where}: {len(missing)} parameters of the aggregator / camera head are not in the checkpoint: {missing[:5]}")
+    if wrong:
+        w = wrong[0]
+        raise ValueError(f"{where}: {len(wrong)} parameters have the wrong shape: {w['key']} is {w['found']}, expected {w['expected']}")
+    if unexpected:
+        raise ValueError(f"{where}: {len(unexpected)} checkpoint tensors are not consumed: {unexpected[:5]}")
+
+
+# ---- RoPE tables and positions (ROPE:86-117, AGG:219-228) ---------------------------------------------------------------------------------
+def rope_tables(max_pos: int, freq: float = 100.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """cos / sin f32 [max_pos + 1][16]: the reference's fp32 angles (position x 1 / freq^(2 i / 32), both fp32), their cosine and sine
+    taken in float64 and rounded once."""
+    exponents = torch.arange(0, 32, 2).float() / 32
+    inv_freq = 1.0 / (freq ** exponents)
+    angles = torch.einsum("i,j->ij", torch.arange(max_pos + 1, dtype=inv_freq.dtype), inv_freq).double()
+    return angles.cos().float().contiguous(), angles.sin().float().contiguous()
+
+
+def token_positions(gh: int, gw: int, n_special: int, frames: int = 1) -> torch.Tensor:
+    """int32 [frames * (n_special + gh gw)][2] = (y, x): special tokens (0, 0), patch (y, x) carries (y + 1, x + 1)."""
+    yx = torch.cartesian_prod(torch.arange(gh), torch.arange(gw)).reshape(gh * gw, 2) + 1
+    one = torch.cat([torch.zeros(n_special, 2, dtype=yx.dtype), yx], 0)
+    return one.repeat(frames, 1).to(torch.int32).contiguous()
+
+
+# ---- pose encoding -> matrices (vggt/utils/pose_enc.py:62-130, rotation.py:14-44) -----------------------------------------------------------
+def pose_encoding_to_extri_intri(pose_enc: torch.Tensor, image_size_hw: Tuple[int, int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """pose_enc [B, S, 9] = (T 3, quaternion xyzw 4, FoV h, FoV w) -> (extrinsic [B, S, 3, 4] = [R | T], intrinsic [B, S, 3, 3])."""
+    T, quat, fov_h, fov_w = pose_enc[..., :3], pose_enc[..., 3:7], pose_enc[..., 7], pose_enc[..., 8]
+    i, j, k, r = torch.unbind(quat, -1)
+    two_s = 2.0 / (quat * quat).sum(-1)
+    R = torch.stack((1 - two_s * (j * j + k * k), two_s * (i * j - k * r), two_s * (i * k + j * r),
+                     two_s * (i * j + k * r), 1 - two_s * (i * i + k * k), two_s * (j * k - i * r),
+                     two_s * (i * k - j * r), two_s * (j * k + i * r), 1 - two_s * (i * i + j * j)), -1).reshape(quat.shape[:-1] + (3, 3))
+    extrinsic = torch.cat([R, T[..., None]], -1)
+    H, W = image_size_hw
+    K = torch.zeros(pose_enc.shape[:-1] + (3, 3), dtype=pose_enc.dtype, device=pose_enc.device)
+    K[..., 0, 0] = (W / 2.0) / torch.tan(fov_w / 2.0)
+    K[..., 1, 1] = (H / 2.0) / torch.tan(fov_h / 2.0)
+    K[..., 0, 2], K[..., 1, 2], K[..., 2, 2] = W / 2, H / 2, 1.0
+    return extrinsic, K
+
+
+# ---- load_and_preprocess_images on PIL images (vggt/utils/load_fn.py:97-215) -----------------------------------------------------------------
+def preprocess(pil_images: Sequence, mode: str = "crop", target: int = 518) -> torch.Tensor:
+    """PIL images -> fp32 [N, 3, H, W] in [0, 1]: RGBA composited over white, width `target`, height rounded to a multiple of 14, PIL
+    bicubic on the uint8 image, centre crop of the height above `target`.  Refused: an empty list, `mode="pad"`, images that end with
+    different shapes (the reference pads those with white)."""
+    from PIL import Image
+    if len(pil_images) == 0:
+        raise ValueError("At least 1 image is required")
+    if mode == "pad":
+        raise NotImplementedError('mode="pad" is not implemented')
+    if mode != "crop":
+        raise ValueError("Mode must be either 'crop' or 'pad'")
+    out = []
+    for img in pil_images:
+        if not isinstance(img, Image.Image):
+            raise TypeError(f"preprocess takes PIL images, got {type(img)}")
+        if img.mode == "RGBA":
+            img = Image.alpha_composite(Image.new("RGBA", img.size, (255, 255, 255, 255)), img)
+        img = img.convert("RGB")
+        w, h = img.size
+        nh = round(h * (target / w) / 14) * 14
+        img = img.resize((target, nh), Image.Resampling.BICUBIC)
+        x = torch.from_numpy(np.asarray(img).copy()).permute(2, 0, 1).to(torch.float32).div(255)
+        if nh > target:
+            y0 = (nh - target) // 2
+            x = x[:, y0:y0 + target]
+        out.append(x.contiguous())
+    if len({tuple(x.shape) for x in out}) > 1:
+        raise NotImplementedError(f"images of mixed shapes {sorted({tuple(x.shape[1:]) for x in out})} are not implemented")
+    return torch.stack(out)
+
+
+class VGGT:
+    def __init__(self, cfg: Optional[VGGTConfig] = None, device="cuda:0"):
+        self.cfg = cfg or VGGTConfig()
+        self.device = torch.device(device)
+        self.W: Dict[str, torch.Tensor] = {}
+        self._pos_cache: Dict[Tuple[int, int], torch.Tensor] = {}
+        self._rope_cache: Dict[Tuple[int, int, int], tuple] = {}
+
+    # ---- weights ---------------------------------------------------------------------------------------------------------------------------
+    def _assemble(self, get):
+        """get(reference key) -> CPU tensor.  Aggregator linears bf16 (rounded once), everything else fp32; the camera head fp32 with its
+        LayerScale folded into proj / fc2 and the 9-wide linears zero-padded to 12."""
+        cfg, dev = self.cfg, self.device
+        f = lambda k: get(k).to(torch.float32).to(dev).contiguous()                      # noqa: E731
+        b = lambda k: get(k).to(torch.float32).to(torch.bfloat16).to(dev).contiguous()   # noqa: E731
+        C = cfg.embed_dim
+        W: Dict[str, torch.Tensor] = {}
+        pe = "aggregator.patch_embed."
+        pw = torch.zeros(C, PATCH_K, dtype=torch.float32)
+        pw[:, :588] = get(pe + "patch_embed.proj.weight").to(torch.float32).reshape(C, 588)
+        W["patch.w"], W["patch.b"] = pw.to(torch.bfloat16).to(dev), f(pe + "patch_embed.proj.bias")
+        W["cls"], W["pos"], W["reg"] = f(pe + "cls_token").reshape(C), f(pe + "pos_embed")[0], f(pe + "register_tokens")[0]
+        W["dnorm.w"], W["dnorm.b"] = f(pe + "norm.weight"), f(pe + "norm.bias")
+        W["cam_tok"], W["reg_tok"] = f("aggregator.camera_token")[0, :, 0], f("aggregator.register_token")[0]
+
+        def block(name, src, qk):
+            for n in ("norm1", "norm2"):
+                W[f"{name}.{n}.w"], W[f"{name}.{n}.b"] = f(f"{src}{n}.weight"), f(f"{src}{n}.bias")
+            for n, k in (("qkv", "attn.qkv"), ("proj", "attn.proj"), ("fc1", "mlp.fc1"), ("fc2", "mlp.fc2")):
+                W[f"{name}.{n}.w"], W[f"{name}.{n}.b"] = b(f"{src}{k}.weight"), f(f"{src}{k}.bias")
+            W[f"{name}.ls1"], W[f"{name}.ls2"] = f(f"{src}ls1.gamma"), f(f"{src}ls2.gamma")
+            if qk:
+                for n in ("q_norm", "k_norm"):
+                    W[f"{name}.{n}.w"], W[f"{name}.{n}.b"] = f(f"{src}attn.{n}.weight"), f(f"{src}attn.{n}.bias")
+
+        for i in range(cfg.dino_depth):
+            block(f"d{i}", f"{pe}blocks.{i}.", False)
+        for i in range(cfg.depth):
+            block(f"f{i}", f"aggregator.frame_blocks.{i}.", True)
+            block(f"g{i}", f"aggregator.global_blocks.{i}.", True)
+
+        ch, D = "camera_head.", cfg.camera_dim
+        for i in range(cfg.camera_trunk_depth):
+            src, name = f"{ch}trunk.{i}.", f"c{i}"
+            for n in ("norm1", "norm2"):
+                W[f"{name}.{n}.w"], W[f"{name}.{n}.b"] = f(f"{src}{n}.weight"), f(f"{src}{n}.bias")
+            W[f"{name}.qkv.w"], W[f"{name}.qkv.b"] = f(f"{src}attn.qkv.weight"), f(f"{src}attn.qkv.bias")
+            W[f"{name}.fc1.w"], W[f"{name}.fc1.b"] = f(f"{src}mlp.fc1.weight"), f(f"{src}mlp.fc1.bias")
+            for n, k, ls in (("proj", "attn.proj", "ls1"), ("fc2", "mlp.fc2", "ls2")):       # LayerScale folded: gamma * (W x + b)
+                g = f(f"{src}{ls}.gamma")
+                W[f"{name}.{n}.w"], W[f"{name}.{n}.b"] = (f(f"{src}{k}.weight") * g[:, None]).contiguous(), f(f"{src}{k}.bias") * g
+        for n in ("token_norm", "trunk_norm"):
+            W[f"{n}.w"], W[f"{n}.b"] = f(f"{ch}{n}.weight"), f(f"{ch}{n}.bias")
+        W["empty_pose"] = f(ch + "empty_pose_tokens").reshape(9)
+        ew = torch.zeros(D, 12, dtype=torch.float32, device=dev)
+        ew[:, :9] = f(ch + "embed_pose.weight")
+        W["embed.w"], W["embed.b"] = ew, f(ch + "embed_pose.bias")
+        W["mod.w"], W["mod.b"] = f(ch + "poseLN_modulation.1.weight"), f(ch + "poseLN_modulation.1.bias")
+        W["pb1.w"], W["pb1.b"] = f(ch + "pose_branch.fc1.weight"), f(ch + "pose_branch.fc1.bias")
+        w2, b2 = torch.zeros(12, D // 2, dtype=torch.float32, device=dev), torch.zeros(12, dtype=torch.float32, device=dev)
+        w2[:9], b2[:9] = f(ch + "pose_branch.fc2.weight"), f(ch + "pose_branch.fc2.bias")
+        W["pb2.w"], W["pb2.b"] = w2, b2
+        self.W = W
+        self._pos_cache.clear()
+        return self
+
+    def init_random(self, seed: int = 0):
+        """Synthetic weights of the configured shapes, generated tensor by tensor from one seeded generator (benchmarks and shape tests)."""
+        g = torch.Generator().manual_seed(seed)
+        shapes = expected_state_dict(self.cfg)
+
+        def get(k):
+            s = shapes[k]
+            if k.endswith(("norm.weight", "norm1.weight", "norm2.weight")):
+                return 1.0 + 0.1 * torch.randn(s, generator=g)
+            if k.endswith(".gamma"):
+                return 0.3 + 0.05 * torch.randn(s, generator=g)
+            if k.endswith(".weight") and len(s) >= 2:
+                fan = int(np.prod(s[1:]))
+                return torch.randn(s, generator=g) * fan ** -0.5
+            if k.endswith("pose_branch.fc2.bias"):
+                return torch.tensor([0.0] * 7 + [1.0, 1.0]) + 0.02 * torch.randn(s, generator=g)
+            return 0.02 * torch.randn(s, generator=g) if not k.endswith(("token", "tokens")) else 0.5 * torch.randn(s, generator=g)
+        return self._assemble(get)
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]):
+        """A state dict under the reference module's key names: the same rules as from_pretrained."""
+        keep = consumed_header({k: {"shape": tuple(v.shape)} for k, v in sd.items()}, "state dict")
+        _raise_on(keep, self.cfg, "state dict")
+        return self._assemble(lambda k: sd[k])
+
+    @classmethod
+    def from_pretrained(cls, folder: str, device="cuda:0"):
+        """`folder/model.safetensors` (+ an optional `config.json`; the defaults are the release).  The header is checked against
+        expected_state_dict before a byte is uploaded: a missing key is a KeyError, an unexpected key or a wrong shape a ValueError."""
+        from . import checkpoint
+        cj = os.path.join(folder, "config.json")
+        cfg = VGGTConfig.from_json(cj) if os.path.exists(cj) else VGGTConfig()
+        path = os.path.join(folder, "model.safetensors")
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"{folder}: no model.safetensors")
+        hdr, _ = checkpoint.read_header(path)
+        keep = consumed_header({k: {"shape": tuple(int(v) for v in e["shape"])} for k, e in hdr.items()}, folder)
+        _raise_on(keep, cfg, folder)
+        sd = checkpoint.load_file(path, keep.keys())     # memory-mapped: a tensor's bytes are read when it is converted
+        return cls(cfg, device)._assemble(lambda k: sd[k])
+
+    # ---- kernels ---------------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _gemm(x, w, bias, out, epi, gate=None):
+        from . import ops
+        from ._ffi import call
+        call("wf_gemm_bf16", x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(),
+             None if gate is None else gate.data_ptr(), x.shape[0], w.shape[0], w.shape[1], x.stride(0), w.stride(0), out.stride(0), epi, ops.stream())
+
+    @staticmethod
+    def _gemm32(x, w, bias, out, epi):
+        from . import ops
+        from ._ffi import call
+        call("wf_gemm_f32", x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), x.shape[0], w.shape[0],
+             w.shape[1], x.stride(0), w.stride(0), out.stride(0), epi, ops.stream())
+
+    @staticmethod
+    def _ln(x, w, b, out, eps):
+        from . import ops
+        from ._ffi import call
+        call("wf_ln_modulate", x.data_ptr(), None if w is None else w.data_ptr(), None if b is None else b.data_ptr(), out.data_ptr(),
+             WF_BF16 if out.dtype == torch.bfloat16 else WF_F32, x.shape[0], x.shape[1], float(eps), 1 if w is None else 0, ops.stream())
+
+    def _block(self, x, name, nseq, L, heads, eps, rope, ws):
+        """One pre-norm block with LayerScale on the fp32 residual stream x [nseq L, C], in place."""
+        from . import ops
+        from ._ffi import call
+        W, st = self.W, ops.stream()
+        M, C = x.shape
+        n, qkv, att, hid, hb = ws["n"][:M], ws["qkv"][:M], ws["att"][:M], ws["hid"][:M], ws["hb"][:M]
+        self._ln(x, W[f"{name}.norm1.w"], W[f"{name}.norm1.b"], n, eps)
+        self._gemm(n, W[f"{name}.qkv.w"], W[f"{name}.qkv.b"], qkv, EPI_BF16)
+        if rope is not None:
+            cs, sn, pos, max_pos = rope
+            call("wf_vit_qk_norm_rope", qkv.data_ptr(), qkv.data_ptr() + 2 * C, 3 * C, W[f"{name}.q_norm.w"].data_ptr(), W[f"{name}.q_norm.b"].data_ptr(),
+                 W[f"{name}.k_norm.w"].data_ptr(), W[f"{name}.k_norm.b"].data_ptr(), 1e-5, cs.data_ptr(), sn.data_ptr(), max_pos, pos.data_ptr(),
+                 nseq, L, heads, 1.0, st)
+        call("wf_vit_attn_fwd", qkv.data_ptr(), qkv.data_ptr() + 2 * C, qkv.data_ptr() + 4 * C, 3 * C, att.data_ptr(), C, nseq, heads, L,
+             0.125, st)
+        self._gemm(att, W[f"{name}.proj.w"], W[f"{name}.proj.b"], x, EPI_RESID, W[f"{name}.ls1"])
+        self._ln(x, W[f"{name}.norm2.w"], W[f"{name}.norm2.b"], n, eps)
+        self._gemm(n, W[f"{name}.fc1.w"], W[f"{name}.fc1.b"], hid, EPI_F32)
+        call("wf_act", hid.data_ptr(), WF_F32, None, WF_F32, hb.data_ptr(), WF_BF16, 1, hid.numel(), st)
+        self._gemm(hb, W[f"{name}.fc2.w"], W[f"{name}.fc2.b"], x, EPI_RESID, W[f"{name}.ls2"])
+
+    def _dino_base(self, gh: int, gw: int) -> torch.Tensor:
+        """fp32 [5 + gh gw, C]: row 0 = cls + pos_0, rows 1..4 the registers (no position), then the position table interpolated to the
+        grid (DINO:180-226: bicubic with antialias, offset 0; the table itself when the grid is the table's)."""
+        if (gh, gw) not in self._pos_cache:
+            cfg, W = self.cfg, self.W
+            pos, M = W["pos"].cpu(), cfg.pos_grid
+            patch = pos[1:]
+            if (gh, gw) != (M, M):
+                patch = torch.nn.functional.interpolate(patch.reshape(1, M, M, -1).permute(0, 3, 1, 2), size=(gh, gw), mode="bicubic",
+                                                        antialias=True).permute(0, 2, 3, 1).reshape(gh * gw, -1)
+            base = torch.cat([(W["cls"].cpu() + pos[0])[None], W["reg"].cpu(), patch], 0)
+            self._pos_cache[(gh, gw)] = base.to(self.device).contiguous()
+        return self._pos_cache[(gh, gw)]
+
+    def _rope(self, gh: int, gw: int, frames: int):
+        key = (gh, gw, frames)
+        if key not in self._rope_cache:
+            max_pos = max(gh, gw)
+            cs, sn = rope_tables(max_pos, self.cfg.rope_freq)
+            pos = token_positions(gh, gw, self.cfg.patch_start_idx, frames)
+            self._rope_cache[key] = (cs.to(self.device), sn.to(self.device), pos.to(self.device), max_pos)
+        return self._rope_cache[key]
+
+    # ---- forward ---------------------------------------------------------------------------------------------------------------------------
+    def _check_images(self, images: torch.Tensor) -> torch.Tensor:
+        if not self.W:
+            raise RuntimeError("VGGT has no weights: from_pretrained, load_state_dict or init_random first")
+        if images.dim() == 4:
+            images = images.unsqueeze(0)
+        if images.dim() != 5 or images.shape[2] != 3 or images.dtype != torch.float32:
+            raise ValueError(f"images must be float32 [S, 3, H, W] or [B, S, 3, H, W], got {images.dtype} {tuple(images.shape)}")
+        if images.shape[0] < 1 or images.shape[1] < 1 or images.shape[3] % 14 or images.shape[4] % 14 or min(images.shape[3:]) < 14:
+            raise ValueError(f"images {tuple(images.shape)}: at least one frame, H and W positive multiples of 14")
+        return images
+
+    def aggregate(self, images: torch.Tensor, keep=KEEP):
+        """images fp32 [S, 3, H, W] or [B, S, 3, H, W] in [0, 1] -> ({layer: fp32 [B, S, 5 + P, 2 C]}, patch_start_idx); `keep="all"`
+        returns every depth."""
+        images = self._check_images(images)
+        cfg = self.cfg
+        layers = tuple(range(cfg.depth)) if isinstance(keep, str) and keep == "all" else tuple(int(k) for k in keep)
+        if any(not 0 <= k < cfg.depth for k in layers):
+            raise ValueError(f"keep {layers}: layers 0..{cfg.depth - 1} exist")
+        per = [self._aggregate_one(images[b].to(self.device).contiguous(), layers) for b in range(images.shape[0])]
+        return {k: torch.stack([p[k] for p in per], 0) for k in layers}, cfg.patch_start_idx
+
+    def _aggregate_one(self, img: torch.Tensor, layers) -> Dict[int, torch.Tensor]:
+        from . import ops
+        from ._ffi import call
+        cfg, W, dev, st = self.cfg, self.W, self.device, ops.stream()
+        S, _, Hh, Ww = img.shape
+        gh, gw = Hh // 14, Ww // 14
+        P, C, F, R = gh * gw, cfg.embed_dim, cfg.hidden, cfg.patch_start_idx
+        T = R + P
+        M = S * T
+        bf, f32 = torch.bfloat16, torch.float32
+        ws = {"n": torch.empty(M, C, dtype=bf, device=dev), "qkv": torch.empty(M, 3 * C, dtype=bf, device=dev),
+              "att": torch.empty(M, C, dtype=bf, device=dev), "hid": torch.empty(M, F, dtype=f32, device=dev),
+              "hb": torch.empty(M, F, dtype=bf, device=dev)}
+        rows = torch.empty(S * P, PATCH_K, dtype=bf, device=dev)
+        call("wf_vit_patch_rows", img.data_ptr(), rows.data_ptr(), S, Hh, Ww, st)
+        x = self._dino_base(gh, gw).unsqueeze(0).repeat(S, 1, 1)                    # [S, T, C]: a device copy
+        for s in range(S):                                                          # patch rows += conv (+ bias) on top of the positions
+            self._gemm(rows[s * P:(s + 1) * P], W["patch.w"], W["patch.b"], x[s, R:], EPI_F32_ACC)
+        x = x.view(M, C)
+        for i in range(cfg.dino_depth):
+            self._block(x, f"d{i}", S, T, cfg.dino_num_heads, cfg.dino_eps, None, ws)
+        xn = torch.empty(M, C, dtype=f32, device=dev)
+        self._ln(x, W["dnorm.w"], W["dnorm.b"], xn, cfg.dino_eps)
+        idx = torch.tensor([0] + [1] * (S - 1), device=dev)
+        tok = torch.cat([W["cam_tok"][idx].unsqueeze(1), W["reg_tok"][idx], xn.view(S, T, C)[:, R:]], 1).contiguous().view(M, C)
+        rope_f, rope_g = self._rope(gh, gw, 1), self._rope(gh, gw, S)
+        out: Dict[int, torch.Tensor] = {}
+        for i in range(cfg.depth):
+            self._block(tok, f"f{i}", S, T, cfg.num_heads, 1e-5, rope_f, ws)
+            fr = tok.clone() if i in layers else None
+            self._block(tok, f"g{i}", 1, M, cfg.num_heads, 1e-5, rope_g, ws)
+            if i in layers:
+                out[i] = torch.cat([fr.view(S, T, C), tok.view(S, T, C)], -1)
+            if i == max(layers):
+                break
+        return out
+
+    def camera_from_tokens(self, tokens: torch.Tensor, num_iterations: Optional[int] = None) -> torch.Tensor:
+        """The camera head on the last kept layer's tokens fp32 [B, S, T, 2 C] -> pose_enc fp32 [B, S, 9] of the last iteration."""
+        from . import ops
+        from ._ffi import call
+        cfg, W, dev, st = self.cfg, self.W, self.device, ops.stream()
+        if not W:
+            raise RuntimeError("VGGT has no weights: from_pretrained, load_state_dict or init_random first")
+        n_it = cfg.camera_iterations if num_iterations is None else int(num_iterations)
+        B, S, _, D = tokens.shape
+        if D != cfg.camera_dim or tokens.dtype != torch.float32 or n_it < 1:
+            raise ValueError(f"tokens must be float32 [B, S, T, {cfg.camera_dim}] and num_iterations >= 1, got {tokens.dtype} {tuple(tokens.shape)}")
+        if S > MAX_FRAMES:
+            raise NotImplementedError(f"{S} frames: wf_clip_attn_fwd over the camera tokens takes at most {MAX_FRAMES}")
+        Hc, f32 = cfg.camera_num_heads, torch.float32
+        hd = D // Hc
+        e = lambda *s: torch.empty(*s, dtype=f32, device=dev)  # noqa: E731
+        res = []
+        for bi in range(B):
+            pose = e(S, D)
+            self._ln(tokens[bi, :, 0].to(dev).contiguous(), W["token_norm.w"], W["token_norm.b"], pose, 1e-5)
+            a = e(S, D)
+            self._ln(pose, None, None, a, 1e-6)                                     # adaln_norm: no affine
+            pred = None
+            inp, emb, mod, n, qkv, att, hid, h2, d12 = torch.zeros(S, 12, dtype=f32, device=dev), e(S, D), e(S, 3 * D), e(S, D), e(S, 3 * D), \
+                e(S, D), e(S, 4 * D), e(S, D // 2), e(S, 12)
+            for _ in range(n_it):
+                inp[:, :9] = W["empty_pose"] if pred is None else pred
+                self._gemm32(inp, W["embed.w"], W["embed.b"], emb, EPI_F32)
+                self._gemm32(torch.nn.functional.silu(emb), W["mod.w"], W["mod.b"], mod, EPI_F32)
+                shift, scale, gate = mod.chunk(3, -1)
+                y = (gate * (a * (1 + scale) + shift) + pose).contiguous()
+                for i in range(cfg.camera_trunk_depth):
+                    c = f"c{i}"
+                    self._ln(y, W[f"{c}.norm1.w"], W[f"{c}.norm1.b"], n, 1e-5)
+                    self._gemm32(n, W[f"{c}.qkv.w"], W[f"{c}.qkv.b"], qkv, EPI_F32)
+                    call("wf_clip_attn_fwd", qkv.data_ptr(), qkv.data_ptr() + 4 * D, qkv.data_ptr() + 8 * D, 3 * D, att.data_ptr(), D, Hc, S, hd,
+                         float(hd) ** -0.5, st)
+                    self._gemm32(att, W[f"{c}.proj.w"], W[f"{c}.proj.b"], y, EPI_F32_ACC)
+                    self._ln(y, W[f"{c}.norm2.w"], W[f"{c}.norm2.b"], n, 1e-5)
+                    self._gemm32(n, W[f"{c}.fc1.w"], W[f"{c}.fc1.b"], hid, EPI_F32_GELU)
+                    self._gemm32(hid, W[f"{c}.fc2.w"], W[f"{c}.fc2.b"], y, EPI_F32_ACC)
+                self._ln(y, W["trunk_norm.w"], W["trunk_norm.b"], n, 1e-5)
+                self._gemm32(n, W["pb1.w"], W["pb1.b"], h2, EPI_F32_GELU)
+                self._gemm32(h2, W["pb2.w"], W["pb2.b"], d12, EPI_F32)
+                pred = d12[:, :9].clone() if pred is None else pred + d12[:, :9]
+            res.append(torch.cat([pred[:, :7], torch.relu(pred[:, 7:])], -1))
+        return torch.stack(res, 0)
+
+    def camera(self, images: torch.Tensor, num_iterations: Optional[int] = None) -> torch.Tensor:
+        """images -> pose_enc fp32 [B, S, 9] (absT_quaR_FoV) of the last iteration."""
+        last = self.cfg.depth - 1
+        toks, _ = self.aggregate(images, keep=(last,))
+        return self.camera_from_tokens(toks[last], num_iterations)
+
+    def cameras(self, images: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """images -> (extrinsic fp32 [B, S, 3, 4], intrinsic fp32 [B, S, 3, 3]) in pixels of the images' own size."""
+        images = self._check_images(images)
+        return pose_encoding_to_extri_intri(self.camera(images), tuple(images.shape[-2:]))
+
+
+def main(argv=None) -> int:
+    import argparse
+    from PIL import Image
+    ap = argparse.ArgumentParser(prog="python -m worldforge_amd.vggt", description="images in, cameras out (VGGT aggregator + camera head)")
+    ap.add_argument("--checkpoint", required=True, help="folder with model.safetensors (+ optional config.json)")
+    ap.add_argument("--images", nargs="+", required=True)
+    ap.add_argument("--out", required=True, help="npz: pose_enc, extrinsic, intrinsic, image_size_hw")
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    x = preprocess([Image.open(p) for p in a.images])
+    model = VGGT.from_pretrained(a.checkpoint, device=a.device)
+    pose = model.camera(x)
+    ext, intr = pose_encoding_to_extri_intri(pose, tuple(x.shape[-2:]))
+    np.savez(a.out, pose_enc=pose.cpu().numpy(), extrinsic=ext.cpu().numpy(), intrinsic=intr.cpu().numpy(),
+             image_size_hw=np.array(x.shape[-2:], dtype=np.int64))
+    print(f"{len(a.images)} images {tuple(x.shape[-2:])} -> {a.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
