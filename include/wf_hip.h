@@ -449,6 +449,37 @@ int wf_vit_qk_norm_rope(void* Q, void* K, int ldqkv, const float* q_weight, cons
  * are zero (wf_gemm_bf16 needs K % 8 == 0: the conv weight is stored [C][592] with the same zero columns).  H, W multiples of 14. */
 int wf_vit_patch_rows(const float* images, void* rows, int n, int H, int W, void* stream);
 
+/* ---- VGGT's DPT depth head (csrc/dpt.hip; vggt/heads/dpt_head.py = DPT, head_act.py; worldforge_amd/vggt.py is the host).  The reference
+ *      runs the head as an fp32 module outside autocast (run_warp.py:234, models/vggt.py:71-76): everything here is fp32 on the fp32-input
+ *      MFMA, activations channels-last f32 [n, H, W, C].  The LayerNorm (DPT:214) is wf_ln_modulate, the 1x1 convolutions (DPT:218, 454,
+ *      output_conv2.2's input side) and the two ConvTransposes with kernel = stride (DPT:76-81) are wf_gemm_f32. ---- */
+/* nn.Conv2d(Cin, Cout, kernel_size=3, stride, padding=1) (DPT:83-85, 102-113, 328-340, 357-358) with what surrounds it fused:
+ *   out[i, y, x, co] = relu_out?( sum_{dy, dx, c} X[i, y stride + dy - 1, x stride + dx - 1, c] w[dy, dx, co, c] + bias[co] + R[i, y, x, co] )
+ *   X = relu_in ? max(in, 0) : in (zero outside the image);  R = resid ? (relu_resid ? max(resid, 0) : resid) : 0.
+ * relu_in + resid + relu_resid is ResidualConvUnit.forward's second half with its in-place ReLU (DPT:376-386: `out = self.activation(x)`
+ * overwrites x, so the skip adds relu(x)); relu_out is output_conv2's ReLU (DPT:111).
+ * in f32 [n, Hi, Wi, Cin]; w_packed f32 [3][3][Cout][Cin] = weight.permute(2, 3, 0, 1) of the module's [Cout][Cin][3][3]; bias f32 [Cout] or
+ * NULL; resid f32 [n, Ho, Wo, Cout] or NULL; out f32 [n, Ho, Wo, Cout], Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1; out may be
+ * neither in nor w_packed (it may be resid: an element is read and written by the same lane).  Every output element is ONE chain of fp32 fma
+ * over taps (dy, dx) outer and channels inner, both ascending, then + bias, + R: its bits depend neither on n nor on the tiling; no atomics,
+ * two calls give the same bits.  WF_EINVAL before any device work unless n, Hi, Wi >= 1, Cin % 4 == 0, Cout % 4 == 0 (both >= 4), stride 1
+ * or 2, in / w_packed / out non-NULL, relu_resid only with resid, every pointer 16-byte aligned, every tensor below 2^31 elements. */
+int wf_conv2d_f32(const float* in, const float* w_packed, const float* bias, const float* resid, float* out, int n, int Hi, int Wi, int Cin,
+                  int Cout, int stride, int relu_in, int relu_resid, int relu_out, void* stream);
+/* custom_interpolate(mode="bilinear", align_corners=True) (DPT:229-234, 453, 459-484) on channels-last maps, in f32 [n, Hi, Wi, C] -> out
+ * f32 [n, Ho, Wo, C], as PyTorch evaluates it in fp32: scale = (in - 1) / (out - 1) (0 when out == 1), src = scale * dst, i0 = (int)src,
+ * i1 = min(i0 + 1, in - 1), l1 = src - i0, l0 = 1 - l1, out = ly0 (lx0 v00 + lx1 v01) + ly1 (lx0 v10 + lx1 v11).  Equal sizes: an exact copy.
+ * _apply_pos_embed (DPT:249-259) fused: col_table f32 [Wo][C / 2] is added to channels 0 .. C/2 - 1 and row_table f32 [Ho][C / 2] to
+ * channels C/2 .. C - 1 of the result; both NULL: none.  WF_EINVAL before any device work unless n and every size >= 1, C % 4 == 0, in / out
+ * non-NULL and 16-byte aligned, the tables both given or both NULL and 4-byte aligned.  out must not overlap in. */
+int wf_resize_bilinear_cl_f32(const float* in, float* out, int n, int Hi, int Wi, int Ho, int Wo, int C, const float* col_table,
+                              const float* row_table, void* stream);
+/* output_conv2.2 (1x1, Cin -> 2; DPT:112) + activate_head(activation="exp", conf_activation="expp1") (head_act.py): rows f32 [npix, Cin],
+ * w f32 [2][Cin], b f32 [2] -> depth f32 [npix] = expf(v0), conf f32 [npix] = 1 + expf(v1), v_j = b[j] + sum_c rows[c] w[j][c] as an fp32 fma
+ * chain over ascending c.  No other activation is built.  WF_EINVAL before any device work unless npix >= 1, Cin % 4 == 0, no pointer NULL,
+ * rows / w 16-byte aligned, b / depth / conf 4-byte aligned. */
+int wf_dpt_depth_out(const float* rows, const float* w, const float* b, float* depth, float* conf, size_t npix, int Cin, void* stream);
+
 /* ---- 3D causal VAE (wan/modules/vae.py; the in-tree statement of diffusers' AutoencoderKLWan), channels-last ----------- */
 /* CausalConv3d / Conv2d as implicit GEMM on MFMA (vae.py:17-36, 76-96, 186-220).  in bf16 [Ti,Hi,Wi,Cin] (Cin % 32 == 0),
  * w bf16 [Cout][kt*kh*kw][Cin], bias f32; out (f32 and/or bf16) [To,Ho,Wo,Cout] (+ resid f32 of the same shape).

@@ -39,6 +39,7 @@ SOURCES = {
     "t5.hip": [],
     "clip.hip": [],
     "vit.hip": [],
+    "dpt.hip": [],
     "vae_ops.hip": [],
     "conv.hip": [],
     "warp.hip": ["-ffp-contract=off"],

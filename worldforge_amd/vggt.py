@@ -1,4 +1,5 @@
-"""VGGT's aggregator and camera head on this engine's own kernels: images in; aggregated tokens, `pose_enc`, extrinsics, intrinsics out.
+"""VGGT's aggregator, camera head and DPT depth head on this engine's own kernels: images in; aggregated tokens, `pose_enc`, extrinsics,
+intrinsics, depth maps and their confidence out.
 
 What the reference runs as `model.aggregator(images)` under bf16 autocast, then `model.camera_head(tokens)` in fp32 (vggt/run_warp.py:212-234;
 AGG = vggt/models/aggregator.py, ATT = vggt/layers/attention.py, ROPE = vggt/layers/rope.py, DINO = vggt/layers/vision_transformer.py,
@@ -17,8 +18,20 @@ per call) on an fp32 residual stream; LayerNorms, LayerScale, tokens and the pos
     camera head (CAM:73-141) on the last layer's camera tokens [S, 2 C]: wf_gemm_f32, wf_clip_attn_fwd (D = 128, L = S), wf_ln_modulate,
     the AdaLN modulate / gate and the activations as torch ops on [S, 2 C].
 
-Not built: the depth / point / track heads (the DPT depth head is the next step: it consumes exactly the four kept layers), `mode="pad"`
-of the preprocessing, images of mixed shapes.
+    depth head (DPT = vggt/heads/dpt_head.py:172-291, opt-in: `depth=True` at load), fp32 throughout like the reference's (run_warp.py:234
+    calls it outside autocast), channels-last maps [n, H, W, C], per chunk of frames, for the four kept layers i = 0..3:
+        rows = wf_ln_modulate(tokens[layer_i][:, 5:])                   the one LayerNorm(2 C), eps 1e-5
+        y    = pos(gh, gw) ; wf_gemm_f32(rows, projects[i]) WF_EPI_F32_ACC      the 1x1 projection on top of the position embedding
+        map  = ConvTranspose k = s = 4 / 2 as wf_gemm_f32 to [pixels, s s Cout] + a pixel shuffle | identity | wf_conv2d_f32 stride 2
+        l_i  = wf_conv2d_f32(map, layer{i+1}_rn)                        bias-free 3x3 to `depth_features` channels
+    fusion (refinenet4 .. 1): out = [out + RCU1(l_i)] ; RCU2(out) ; the 1x1 out_conv (wf_gemm_f32) ; wf_resize_bilinear_cl_f32 to the next
+        map's size -- the 1x1 runs BEFORE the resize (both are linear and the bilinear weights sum to one: a quarter of its FLOPs);
+        RCU(x) = conv2(relu(conv1(relu(x)))) + relu(x) in two wf_conv2d_f32 calls: the reference's ReLU is in place, so the skip is relu(x)
+    head: output_conv1 ; resize to (14 gh, 14 gw) + position tables ; output_conv2.0 + ReLU ; wf_dpt_depth_out (1x1 to 2, exp / 1 + exp).
+    The position embedding (vggt/heads/utils.py) is separable: a column table [w][C / 2] and a row table [h][C / 2], built on the host with
+    the reference's own torch calls and cached per shape (dpt_pos_tables).
+
+Not built: the point / track heads, DPTHead's `feature_only` and `down_ratio != 1`, `mode="pad"` of the preprocessing, images of mixed shapes.
 """
 from __future__ import annotations
 
@@ -61,6 +74,9 @@ class VGGTConfig:
     camera_trunk_depth: int = 4
     camera_num_heads: int = 16
     camera_iterations: int = 4
+    depth_features: int = 256
+    depth_out_channels: Tuple[int, ...] = (256, 512, 1024, 1024)
+    depth_layers: Tuple[int, ...] = (4, 11, 17, 23)
 
     @property
     def patch_start_idx(self) -> int:
@@ -83,6 +99,9 @@ class VGGTConfig:
         d = dict(d)
         if "aa_order" in d:
             d["aa_order"] = tuple(d["aa_order"])
+        for k in ("depth_out_channels", "depth_layers"):
+            if k in d:
+                d[k] = tuple(int(v) for v in d[k])
         cfg = cls(**{k: d[k] for k in cls.__dataclass_fields__ if k in d})
         if cfg.patch_size != 14:
             raise NotImplementedError(f"patch_size {cfg.patch_size}: wf_vit_patch_rows is built for 14")
@@ -104,7 +123,19 @@ class VGGTConfig:
             raise NotImplementedError("camera trunk head width: wf_clip_attn_fwd takes multiples of 8 in 8..128")
         if min(cfg.depth, cfg.dino_depth, cfg.camera_trunk_depth, cfg.num_register_tokens, cfg.img_size) < 1 or cfg.img_size % 14:
             raise ValueError("depths, register tokens and img_size must be positive, img_size a multiple of 14")
+        if len(cfg.depth_layers) != 4 or len(cfg.depth_out_channels) != 4:
+            raise NotImplementedError(f"depth_layers {list(cfg.depth_layers)} / depth_out_channels {list(cfg.depth_out_channels)}: the DPT head "
+                                      "is built for four kept layers")
+        if cfg.depth_features < 8 or cfg.depth_features % 8 or any(c < 4 or c % 4 for c in cfg.depth_out_channels):
+            raise NotImplementedError(f"depth_features {cfg.depth_features} / depth_out_channels {list(cfg.depth_out_channels)}: wf_conv2d_f32 "
+                                      "takes channel counts that are multiples of 4 (depth_features / 2 included)")
+        if "depth_layers" in d:      # a config that does not name them (no depth head in its checkpoint) is checked when the head is loaded
+            cfg.check_depth_layers()
         return cfg
+
+    def check_depth_layers(self):
+        if any(not 0 <= k < self.depth for k in self.depth_layers):
+            raise ValueError(f"depth_layers {list(self.depth_layers)}: layers 0..{self.depth - 1} exist")
 
     @classmethod
     def from_json(cls, path: str) -> "VGGTConfig":
@@ -127,9 +158,32 @@ def _block_keys(prefix: str, C: int, F: int, qk_norm: bool) -> Dict[str, Tuple[i
     return out
 
 
-def expected_state_dict(cfg: VGGTConfig) -> Dict[str, Tuple[int, ...]]:
+def depth_head_keys(cfg: VGGTConfig) -> Dict[str, Tuple[int, ...]]:
+    """{key: shape} of DPTHead(dim_in = 2 C, output_dim = 2, features, out_channels) under `depth_head.` (DPT:66-113, 299-341)."""
+    D, f, oc, dh = cfg.camera_dim, cfg.depth_features, cfg.depth_out_channels, "depth_head."
+    out: Dict[str, Tuple[int, ...]] = {dh + "norm.weight": (D,), dh + "norm.bias": (D,)}
+    for i, c in enumerate(oc):
+        out[f"{dh}projects.{i}.weight"], out[f"{dh}projects.{i}.bias"] = (c, D, 1, 1), (c,)
+    for i, k in ((0, 4), (1, 2), (3, 3)):
+        out[f"{dh}resize_layers.{i}.weight"], out[f"{dh}resize_layers.{i}.bias"] = (oc[i], oc[i], k, k), (oc[i],)
+    sc = dh + "scratch."
+    for i, c in enumerate(oc):
+        out[f"{sc}layer{i + 1}_rn.weight"] = (f, c, 3, 3)
+    for i in (1, 2, 3, 4):
+        r = f"{sc}refinenet{i}."
+        out[r + "out_conv.weight"], out[r + "out_conv.bias"] = (f, f, 1, 1), (f,)
+        for u in (("resConfUnit1", "resConfUnit2") if i < 4 else ("resConfUnit2",)):
+            for c in ("conv1", "conv2"):
+                out[f"{r}{u}.{c}.weight"], out[f"{r}{u}.{c}.bias"] = (f, f, 3, 3), (f,)
+    out.update({sc + "output_conv1.weight": (f // 2, f, 3, 3), sc + "output_conv1.bias": (f // 2,),
+                sc + "output_conv2.0.weight": (32, f // 2, 3, 3), sc + "output_conv2.0.bias": (32,),
+                sc + "output_conv2.2.weight": (2, 32, 1, 1), sc + "output_conv2.2.bias": (2,)})
+    return out
+
+
+def expected_state_dict(cfg: VGGTConfig, depth: bool = False) -> Dict[str, Tuple[int, ...]]:
     """{key of the reference's VGGT module: shape} of everything this engine uploads: `aggregator.*` (without the DINOv2 mask token) and
-    `camera_head.*`."""
+    `camera_head.*`; with `depth=True` also `depth_head.*`."""
     C, F, R, D = cfg.embed_dim, cfg.hidden, cfg.num_register_tokens, cfg.camera_dim
     out: Dict[str, Tuple[int, ...]] = {"aggregator.camera_token": (1, 2, 1, C), "aggregator.register_token": (1, 2, R, C)}
     pe = "aggregator.patch_embed."
@@ -149,24 +203,31 @@ def expected_state_dict(cfg: VGGTConfig) -> Dict[str, Tuple[int, ...]]:
                 ch + "poseLN_modulation.1.weight": (3 * D, D), ch + "poseLN_modulation.1.bias": (3 * D,),
                 ch + "pose_branch.fc1.weight": (D // 2, D), ch + "pose_branch.fc1.bias": (D // 2,),
                 ch + "pose_branch.fc2.weight": (9, D // 2), ch + "pose_branch.fc2.bias": (9,)})
+    if depth:
+        out.update(depth_head_keys(cfg))
     return out
 
 
-def consumed_header(found: Dict[str, dict], where: str = "checkpoint") -> Dict[str, dict]:
-    """The entries this engine uploads; the heads that are not built and the DINOv2 mask token are dropped with ONE warning."""
-    keep = {k: v for k, v in found.items() if not k.startswith(IGNORED)}
+def consumed_header(found: Dict[str, dict], where: str = "checkpoint", depth: bool = False) -> Dict[str, dict]:
+    """The entries this engine uploads; the heads that are not built (or, without `depth=True`, not asked for) and the DINOv2 mask token
+    are dropped with ONE warning.  With `depth=True` the `depth_head.*` entries are kept and checked like every other."""
+    ignored = tuple(g for g in IGNORED if not (depth and g == "depth_head."))
+    keep = {k: v for k, v in found.items() if not k.startswith(ignored)}
     if len(keep) != len(found):
-        groups = sorted({g for g in IGNORED for k in found if k.startswith(g)})
+        groups = sorted({g for g in ignored for k in found if k.startswith(g)})
         warnings.warn(f"{where}: {len(found) - len(keep)} tensors of {', '.join(groups)} are not consumed (heads not built here) and are ignored",
                       UserWarning, stacklevel=3)
     return keep
 
 
-def _raise_on(keep: Dict[str, dict], cfg: VGGTConfig, where: str):
+def _raise_on(keep: Dict[str, dict], cfg: VGGTConfig, where: str, depth: bool = False):
     from .checkpoint import compare_header
-    missing, unexpected, wrong = compare_header(keep, expected_state_dict(cfg))
+    if depth:
+        cfg.check_depth_layers()
+    missing, unexpected, wrong = compare_header(keep, expected_state_dict(cfg, depth))
     if missing:
-        raise KeyError(f"{where}: {len(missing)} parameters of the aggregator / camera head are not in the checkpoint: {missing[:5]}")
+        raise KeyError(f"{where}: {len(missing)} parameters of the aggregator / camera head{' / depth head' if depth else ''} are not in the "
+                       f"checkpoint: {missing[:5]}")
     if wrong:
         w = wrong[0]
         raise ValueError(f"{where}: {len(wrong)} parameters have the wrong shape: {w['key']} is {w['found']}, expected {w['expected']}")
@@ -189,6 +250,56 @@ def token_positions(gh: int, gw: int, n_special: int, frames: int = 1) -> torch.
     yx = torch.cartesian_prod(torch.arange(gh), torch.arange(gw)).reshape(gh * gw, 2) + 1
     one = torch.cat([torch.zeros(n_special, 2, dtype=yx.dtype), yx], 0)
     return one.repeat(frames, 1).to(torch.int32).contiguous()
+
+
+# ---- the DPT head's position embedding (DPT:249-259, vggt/heads/utils.py) ------------------------------------------------------------------
+def dpt_pos_tables(C: int, h: int, w: int, image_hw: Tuple[int, int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """_apply_pos_embed's addend for a [C, h, w] map of an image of size image_hw, as its two factors: (col f32 [w][C / 2], row f32
+    [h][C / 2]); channel c < C / 2 of pixel (y, x) receives col[x][c], channel c >= C / 2 receives row[y][c - C / 2].  Built with the
+    reference's own torch calls, so bit-equal to it: the coordinate is an fp32 linspace over -+span (n - 1) / n (span_x = a / sqrt(a^2 + 1),
+    span_y = 1 / sqrt(a^2 + 1), a = W / H of the image), the angles coordinate x 100^(-k / (C / 4)) are float64, [sin | cos] is rounded
+    to fp32 and then multiplied by 0.1 in fp32."""
+    if C % 4:
+        raise ValueError(f"dpt_pos_tables: {C} channels: each axis takes C / 2 channels, half sines and half cosines")
+    H, W = image_hw
+    aspect = W / H
+    diag = (aspect ** 2 + 1.0) ** 0.5
+    span_x, span_y = aspect / diag, 1.0 / diag
+    xs = torch.linspace(-span_x * (w - 1) / w, span_x * (w - 1) / w, steps=w, dtype=torch.float32)
+    ys = torch.linspace(-span_y * (h - 1) / h, span_y * (h - 1) / h, steps=h, dtype=torch.float32)
+    omega = torch.arange(C // 4, dtype=torch.double)
+    omega /= (C // 2) / 2.0
+    omega = 1.0 / 100 ** omega
+
+    def table(pos):
+        out = torch.einsum("m,d->md", pos, omega)
+        return (torch.cat([torch.sin(out), torch.cos(out)], dim=1).float() * 0.1).contiguous()
+    return table(xs), table(ys)
+
+
+def dpt_pos_embed(C: int, h: int, w: int, image_hw: Tuple[int, int]) -> torch.Tensor:
+    """The two tables expanded to the reference's addend, f32 [C, h, w] (the patch grids and the tests; never the full-resolution map)."""
+    col, row = dpt_pos_tables(C, h, w, image_hw)
+    return torch.cat([col.t()[:, None, :].expand(C // 2, h, w), row.t()[:, :, None].expand(C // 2, h, w)], 0).contiguous()
+
+
+def to_image_size(depth: torch.Tensor, depth_conf: torch.Tensor, intrinsic: torch.Tensor, model_hw: Tuple[int, int], orig_hw: Tuple[int, int]):
+    """The hand-over to stage 1 (run_warp.py:273-292): depth f32 [..., H, W, 1] and depth_conf f32 [..., H, W] at the model's size ->
+    the original image's size with half-pixel bilinear (cv2.INTER_LINEAR on float maps = wf_resize_bilinear2d), and the intrinsics
+    [..., 3, 3] with fx, cx scaled by orig_w / model_w and fy, cy by orig_h / model_h.  -> (depth [..., h, w, 1], conf [..., h, w], K)."""
+    from . import ops
+    (H, W), (oh, ow) = model_hw, orig_hw
+    if tuple(depth.shape[-3:]) != (H, W, 1) or tuple(depth_conf.shape[-2:]) != (H, W) or tuple(intrinsic.shape[-2:]) != (3, 3):
+        raise ValueError(f"to_image_size: depth {tuple(depth.shape)}, depth_conf {tuple(depth_conf.shape)}, intrinsic {tuple(intrinsic.shape)} "
+                         f"do not match the model size {(H, W)}")
+    d = ops.resize_bilinear2d(depth.squeeze(-1).contiguous(), oh, ow).unsqueeze(-1)
+    c = ops.resize_bilinear2d(depth_conf.contiguous(), oh, ow)
+    K = intrinsic.clone()
+    K[..., 0, 0] *= ow / W
+    K[..., 0, 2] *= ow / W
+    K[..., 1, 1] *= oh / H
+    K[..., 1, 2] *= oh / H
+    return d, c, K
 
 
 # ---- pose encoding -> matrices (vggt/utils/pose_enc.py:62-130, rotation.py:14-44) -----------------------------------------------------------
@@ -248,11 +359,13 @@ class VGGT:
         self.W: Dict[str, torch.Tensor] = {}
         self._pos_cache: Dict[Tuple[int, int], torch.Tensor] = {}
         self._rope_cache: Dict[Tuple[int, int, int], tuple] = {}
+        self._dpt_cache: Dict[tuple, tuple] = {}
+        self.has_depth = False
 
     # ---- weights ---------------------------------------------------------------------------------------------------------------------------
-    def _assemble(self, get):
+    def _assemble(self, get, depth: bool = False):
         """get(reference key) -> CPU tensor.  Aggregator linears bf16 (rounded once), everything else fp32; the camera head fp32 with its
-        LayerScale folded into proj / fc2 and the 9-wide linears zero-padded to 12."""
+        LayerScale folded into proj / fc2 and the 9-wide linears zero-padded to 12; `depth`: the DPT head too (_assemble_depth)."""
         cfg, dev = self.cfg, self.device
         f = lambda k: get(k).to(torch.float32).to(dev).contiguous()                      # noqa: E731
         b = lambda k: get(k).to(torch.float32).to(torch.bfloat16).to(dev).contiguous()   # noqa: E731
@@ -303,14 +416,46 @@ class VGGT:
         w2, b2 = torch.zeros(12, D // 2, dtype=torch.float32, device=dev), torch.zeros(12, dtype=torch.float32, device=dev)
         w2[:9], b2[:9] = f(ch + "pose_branch.fc2.weight"), f(ch + "pose_branch.fc2.bias")
         W["pb2.w"], W["pb2.b"] = w2, b2
+        if depth:
+            self._assemble_depth(W, f)
         self.W = W
+        self.has_depth = bool(depth)
         self._pos_cache.clear()
+        self._dpt_cache.clear()
         return self
 
-    def init_random(self, seed: int = 0):
-        """Synthetic weights of the configured shapes, generated tensor by tensor from one seeded generator (benchmarks and shape tests)."""
+    def _assemble_depth(self, W, f):
+        """The DPT head, fp32: 3x3 weights packed [3][3][Cout][Cin] for wf_conv2d_f32, 1x1 weights as [Cout, Cin], the ConvTranspose
+        weights [Cin][Cout][s][s] as the GEMM operand [(ky, kx, Cout)][Cin] with the bias repeated s s times."""
+        dh, sc = "depth_head.", "depth_head.scratch."
+        pack = lambda k: f(k).permute(2, 3, 0, 1).contiguous()                           # noqa: E731
+        flat = lambda k: f(k).flatten(1).contiguous()                                    # noqa: E731
+        W["dpt.norm.w"], W["dpt.norm.b"] = f(dh + "norm.weight"), f(dh + "norm.bias")
+        for i in range(4):
+            W[f"dpt.proj{i}.w"], W[f"dpt.proj{i}.b"] = flat(f"{dh}projects.{i}.weight"), f(f"{dh}projects.{i}.bias")
+            W[f"dpt.rn{i}.w"] = pack(f"{sc}layer{i + 1}_rn.weight")
+        for i, s in ((0, 4), (1, 2)):
+            w = f(f"{dh}resize_layers.{i}.weight")
+            W[f"dpt.up{i}.w"] = w.permute(2, 3, 1, 0).reshape(s * s * w.shape[1], w.shape[0]).contiguous()
+            W[f"dpt.up{i}.b"] = f(f"{dh}resize_layers.{i}.bias").repeat(s * s).contiguous()
+        W["dpt.down.w"], W["dpt.down.b"] = pack(dh + "resize_layers.3.weight"), f(dh + "resize_layers.3.bias")
+        for i in (1, 2, 3, 4):
+            r = f"{sc}refinenet{i}."
+            W[f"dpt.ref{i}.out.w"], W[f"dpt.ref{i}.out.b"] = flat(r + "out_conv.weight"), f(r + "out_conv.bias")
+            for u, name in ((("resConfUnit1", "rcu1"), ("resConfUnit2", "rcu2")) if i < 4 else (("resConfUnit2", "rcu2"),)):
+                for c, cn in (("conv1", "c1"), ("conv2", "c2")):
+                    W[f"dpt.ref{i}.{name}.{cn}.w"], W[f"dpt.ref{i}.{name}.{cn}.b"] = pack(f"{r}{u}.{c}.weight"), f(f"{r}{u}.{c}.bias")
+        W["dpt.oc1.w"], W["dpt.oc1.b"] = pack(sc + "output_conv1.weight"), f(sc + "output_conv1.bias")
+        W["dpt.oc2.w"], W["dpt.oc2.b"] = pack(sc + "output_conv2.0.weight"), f(sc + "output_conv2.0.bias")
+        W["dpt.oc3.w"], W["dpt.oc3.b"] = flat(sc + "output_conv2.2.weight"), f(sc + "output_conv2.2.bias")
+
+    def init_random(self, seed: int = 0, depth: bool = False):
+        """Synthetic weights of the configured shapes, generated tensor by tensor from one seeded generator (benchmarks and shape tests).
+        The aggregator's and the camera head's are the same with and without `depth=True`: the depth head's are drawn after them."""
         g = torch.Generator().manual_seed(seed)
-        shapes = expected_state_dict(self.cfg)
+        if depth:
+            self.cfg.check_depth_layers()
+        shapes = expected_state_dict(self.cfg, depth)
 
         def get(k):
             s = shapes[k]
@@ -324,18 +469,19 @@ class VGGT:
             if k.endswith("pose_branch.fc2.bias"):
                 return torch.tensor([0.0] * 7 + [1.0, 1.0]) + 0.02 * torch.randn(s, generator=g)
             return 0.02 * torch.randn(s, generator=g) if not k.endswith(("token", "tokens")) else 0.5 * torch.randn(s, generator=g)
-        return self._assemble(get)
+        return self._assemble(get, depth)
 
-    def load_state_dict(self, sd: Dict[str, torch.Tensor]):
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], depth: bool = False):
         """A state dict under the reference module's key names: the same rules as from_pretrained."""
-        keep = consumed_header({k: {"shape": tuple(v.shape)} for k, v in sd.items()}, "state dict")
-        _raise_on(keep, self.cfg, "state dict")
-        return self._assemble(lambda k: sd[k])
+        keep = consumed_header({k: {"shape": tuple(v.shape)} for k, v in sd.items()}, "state dict", depth)
+        _raise_on(keep, self.cfg, "state dict", depth)
+        return self._assemble(lambda k: sd[k], depth)
 
     @classmethod
-    def from_pretrained(cls, folder: str, device="cuda:0"):
+    def from_pretrained(cls, folder: str, device="cuda:0", depth: bool = False):
         """`folder/model.safetensors` (+ an optional `config.json`; the defaults are the release).  The header is checked against
-        expected_state_dict before a byte is uploaded: a missing key is a KeyError, an unexpected key or a wrong shape a ValueError."""
+        expected_state_dict before a byte is uploaded: a missing key is a KeyError, an unexpected key or a wrong shape a ValueError.
+        `depth=True` also loads the DPT depth head (`depth_head.*`, checked in the same way); without it those tensors are ignored."""
         from . import checkpoint
         cj = os.path.join(folder, "config.json")
         cfg = VGGTConfig.from_json(cj) if os.path.exists(cj) else VGGTConfig()
@@ -343,10 +489,10 @@ class VGGT:
         if not os.path.exists(path):
             raise FileNotFoundError(f"{folder}: no model.safetensors")
         hdr, _ = checkpoint.read_header(path)
-        keep = consumed_header({k: {"shape": tuple(int(v) for v in e["shape"])} for k, e in hdr.items()}, folder)
-        _raise_on(keep, cfg, folder)
+        keep = consumed_header({k: {"shape": tuple(int(v) for v in e["shape"])} for k, e in hdr.items()}, folder, depth)
+        _raise_on(keep, cfg, folder, depth)
         sd = checkpoint.load_file(path, keep.keys())     # memory-mapped: a tensor's bytes are read when it is converted
-        return cls(cfg, device)._assemble(lambda k: sd[k])
+        return cls(cfg, device)._assemble(lambda k: sd[k], depth)
 
     # ---- kernels ---------------------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -534,6 +680,144 @@ class VGGT:
         images = self._check_images(images)
         return pose_encoding_to_extri_intri(self.camera(images), tuple(images.shape[-2:]))
 
+    # ---- the DPT depth head ----------------------------------------------------------------------------------------------------------------
+    def _need_depth(self):
+        if not self.W:
+            raise RuntimeError("VGGT has no weights: from_pretrained, load_state_dict or init_random first")
+        if not self.has_depth:
+            raise RuntimeError("this VGGT was loaded without the depth head: load it with depth=True "
+                               "(from_pretrained / load_state_dict / init_random)")
+
+    def _conv(self, x, name, stride=1, relu_in=False, resid=None, relu_resid=False, relu_out=False):
+        """wf_conv2d_f32 on a contiguous channels-last map x f32 [n, Hi, Wi, Cin] with the packed weight `name`.w (and `name`.b if any)."""
+        from . import ops
+        from ._ffi import call
+        w, b = self.W[name + ".w"], self.W.get(name + ".b")
+        n, Hi, Wi, Cin = x.shape
+        out = torch.empty(n, (Hi - 1) // stride + 1, (Wi - 1) // stride + 1, w.shape[2], dtype=torch.float32, device=self.device)
+        call("wf_conv2d_f32", x.data_ptr(), w.data_ptr(), None if b is None else b.data_ptr(), None if resid is None else resid.data_ptr(),
+             out.data_ptr(), n, Hi, Wi, Cin, w.shape[2], stride, int(relu_in), int(relu_resid), int(relu_out), ops.stream())
+        return out
+
+    def _resize(self, x, Ho, Wo, tables=None):
+        from . import ops
+        from ._ffi import call
+        n, Hi, Wi, C = x.shape
+        out = torch.empty(n, Ho, Wo, C, dtype=torch.float32, device=self.device)
+        col, row = tables if tables is not None else (None, None)
+        call("wf_resize_bilinear_cl_f32", x.data_ptr(), out.data_ptr(), n, Hi, Wi, Ho, Wo, C, None if col is None else col.data_ptr(),
+             None if row is None else row.data_ptr(), ops.stream())
+        return out
+
+    def _dpt_tables(self, C, h, w, image_hw, expanded=False):
+        """The position tables on the device, cached per shape; `expanded`: the addend of a patch grid as rows f32 [h w, C]."""
+        key = (C, h, w, tuple(image_hw), expanded)
+        if key not in self._dpt_cache:
+            if expanded:
+                self._dpt_cache[key] = (dpt_pos_embed(C, h, w, image_hw).permute(1, 2, 0).reshape(h * w, C).contiguous().to(self.device),)
+            else:
+                self._dpt_cache[key] = tuple(t.to(self.device) for t in dpt_pos_tables(C, h, w, image_hw))
+        return self._dpt_cache[key]
+
+    def _rcu(self, x, name):
+        """ResidualConvUnit (DPT:366-386) with its in-place ReLU: conv2(relu(conv1(relu(x)))) + relu(x)."""
+        t = self._conv(x, name + ".c1", relu_in=True)
+        return self._conv(t, name + ".c2", relu_in=True, resid=x, relu_resid=True)
+
+    def _fuse(self, out, skip, name, size):
+        """FeatureFusionBlock (DPT:432-456); the 1x1 out_conv runs before the resize (see the module docstring)."""
+        if skip is not None:
+            out = out + self._rcu(skip, name + ".rcu1")
+        out = self._rcu(out, name + ".rcu2")
+        n, h, w, f = out.shape
+        o = torch.empty(n * h * w, f, dtype=torch.float32, device=self.device)
+        self._gemm32(out.view(n * h * w, f), self.W[name + ".out.w"], self.W[name + ".out.b"], o, EPI_F32)
+        return self._resize(o.view(n, h, w, f), size[0], size[1])
+
+    def _depth_chunk(self, xs, gh, gw, image_hw, depth_out, conf_out):
+        """DPT._forward_impl on n frames: xs = the four kept layers' patch tokens [n, P, 2 C] -> depth_out / conf_out f32 [n, H, W]."""
+        from . import ops
+        from ._ffi import call
+        cfg, W, dev, f32 = self.cfg, self.W, self.device, torch.float32
+        n, P, D = xs[0].shape
+        maps = []
+        for i, oc in enumerate(cfg.depth_out_channels):
+            x = xs[i].to(dev).reshape(n * P, D).contiguous()
+            xn = torch.empty_like(x)
+            self._ln(x, W["dpt.norm.w"], W["dpt.norm.b"], xn, 1e-5)
+            y = self._dpt_tables(oc, gh, gw, image_hw, expanded=True)[0].repeat(n, 1)       # the projection lands on top of the positions
+            self._gemm32(xn, W[f"dpt.proj{i}.w"], W[f"dpt.proj{i}.b"], y, EPI_F32_ACC)
+            if i < 2:                                                                     # ConvTranspose, kernel = stride = s
+                s = 4 if i == 0 else 2
+                g = torch.empty(n * P, s * s * oc, dtype=f32, device=dev)
+                self._gemm32(y, W[f"dpt.up{i}.w"], W[f"dpt.up{i}.b"], g, EPI_F32)
+                m = g.view(n, gh, gw, s, s, oc).permute(0, 1, 3, 2, 4, 5).reshape(n, gh * s, gw * s, oc).contiguous()
+            elif i == 2:
+                m = y.view(n, gh, gw, oc)
+            else:
+                m = self._conv(y.view(n, gh, gw, oc), "dpt.down", stride=2)
+            maps.append(self._conv(m, f"dpt.rn{i}"))
+        l1, l2, l3, l4 = maps
+        out = self._fuse(l4, None, "dpt.ref4", l3.shape[1:3])
+        out = self._fuse(out, l3, "dpt.ref3", l2.shape[1:3])
+        out = self._fuse(out, l2, "dpt.ref2", l1.shape[1:3])
+        out = self._fuse(out, l1, "dpt.ref1", (2 * l1.shape[1], 2 * l1.shape[2]))
+        out = self._conv(out, "dpt.oc1")
+        out = self._resize(out, 14 * gh, 14 * gw, self._dpt_tables(out.shape[3], 14 * gh, 14 * gw, image_hw))
+        out = self._conv(out, "dpt.oc2", relu_out=True)
+        call("wf_dpt_depth_out", out.data_ptr(), W["dpt.oc3.w"].data_ptr(), W["dpt.oc3.b"].data_ptr(), depth_out.data_ptr(), conf_out.data_ptr(),
+             n * 14 * gh * 14 * gw, out.shape[3], ops.stream())
+
+    def depth_from_tokens(self, tokens: Dict[int, torch.Tensor], image_hw: Tuple[int, int], frames_chunk_size: Optional[int] = 8,
+                          layers: Optional[Sequence[int]] = None):
+        """The depth head on the kept layers {layer: fp32 [B, S, 5 + P, 2 C]} of images of size image_hw -> (depth fp32 [B, S, H, W, 1],
+        depth_conf fp32 [B, S, H, W]).  Frames are processed in chunks of frames_chunk_size (None: all at once; DPT:139-170); the result
+        does not depend on the chunk size, bit for bit.  `layers`: the four keys of `tokens` in the head's order (default: the
+        configuration's depth_layers, the keys aggregate() returns)."""
+        self._need_depth()
+        cfg, dev = self.cfg, self.device
+        H, W = (int(v) for v in image_hw)
+        if H < 14 or W < 14 or H % 14 or W % 14:
+            raise ValueError(f"image_hw {(H, W)}: H and W are positive multiples of 14")
+        gh, gw, R = H // 14, W // 14, cfg.patch_start_idx
+        layers = tuple(cfg.depth_layers if layers is None else layers)
+        missing = [k for k in layers if k not in tokens]
+        if missing or len(layers) != 4:
+            raise ValueError(f"depth_from_tokens: four layers are needed, {missing} of {list(layers)} are not in the tokens")
+        B, S = tokens[layers[0]].shape[:2]
+        for k in layers:
+            t = tokens[k]
+            if t.dtype != torch.float32 or tuple(t.shape) != (B, S, R + gh * gw, cfg.camera_dim):
+                raise ValueError(f"tokens[{k}] must be float32 {(B, S, R + gh * gw, cfg.camera_dim)}, got {t.dtype} {tuple(t.shape)}")
+        if frames_chunk_size is not None and int(frames_chunk_size) < 1:
+            raise ValueError(f"frames_chunk_size {frames_chunk_size}: at least 1, or None")
+        chunk = S if frames_chunk_size is None else min(int(frames_chunk_size), S)
+        depth = torch.empty(B, S, H, W, dtype=torch.float32, device=dev)
+        conf = torch.empty(B, S, H, W, dtype=torch.float32, device=dev)
+        for b in range(B):
+            for s0 in range(0, S, chunk):
+                s1 = min(s0 + chunk, S)
+                self._depth_chunk([tokens[k][b, s0:s1, R:] for k in layers], gh, gw, (H, W), depth[b, s0:s1], conf[b, s0:s1])
+        return depth.unsqueeze(-1), conf
+
+    def depth(self, images: torch.Tensor, frames_chunk_size: Optional[int] = 8) -> Tuple[torch.Tensor, torch.Tensor]:
+        """images -> (depth fp32 [B, S, H, W, 1], depth_conf fp32 [B, S, H, W]): aggregate + depth head."""
+        self._need_depth()
+        images = self._check_images(images)
+        toks, _ = self.aggregate(images, keep=self.cfg.depth_layers)
+        return self.depth_from_tokens(toks, tuple(images.shape[-2:]), frames_chunk_size)
+
+    def predict(self, images: torch.Tensor, frames_chunk_size: Optional[int] = 8) -> Dict[str, torch.Tensor]:
+        """images -> {pose_enc, extrinsic, intrinsic, depth, depth_conf}: ONE aggregator pass serves the camera head and the depth head."""
+        self._need_depth()
+        images = self._check_images(images)
+        last, hw = self.cfg.depth - 1, tuple(images.shape[-2:])
+        toks, _ = self.aggregate(images, keep=tuple(self.cfg.depth_layers) + (last,))
+        pose = self.camera_from_tokens(toks[last])
+        ext, intr = pose_encoding_to_extri_intri(pose, hw)
+        depth, conf = self.depth_from_tokens(toks, hw, frames_chunk_size)
+        return {"pose_enc": pose, "extrinsic": ext, "intrinsic": intr, "depth": depth, "depth_conf": conf}
+
 
 def main(argv=None) -> int:
     import argparse
@@ -543,13 +827,20 @@ def main(argv=None) -> int:
     ap.add_argument("--images", nargs="+", required=True)
     ap.add_argument("--out", required=True, help="npz: pose_enc, extrinsic, intrinsic, image_size_hw")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--depth", action="store_true", help="load the DPT depth head too and add depth [1, S, H, W, 1], depth_conf [1, S, H, W] to the npz")
     a = ap.parse_args(argv)
     x = preprocess([Image.open(p) for p in a.images])
-    model = VGGT.from_pretrained(a.checkpoint, device=a.device)
-    pose = model.camera(x)
-    ext, intr = pose_encoding_to_extri_intri(pose, tuple(x.shape[-2:]))
+    model = VGGT.from_pretrained(a.checkpoint, device=a.device, depth=a.depth)
+    extra = {}
+    if a.depth:
+        r = model.predict(x)
+        pose, ext, intr = r["pose_enc"], r["extrinsic"], r["intrinsic"]
+        extra = {"depth": r["depth"].cpu().numpy(), "depth_conf": r["depth_conf"].cpu().numpy()}
+    else:
+        pose = model.camera(x)
+        ext, intr = pose_encoding_to_extri_intri(pose, tuple(x.shape[-2:]))
     np.savez(a.out, pose_enc=pose.cpu().numpy(), extrinsic=ext.cpu().numpy(), intrinsic=intr.cpu().numpy(),
-             image_size_hw=np.array(x.shape[-2:], dtype=np.int64))
+             image_size_hw=np.array(x.shape[-2:], dtype=np.int64), **extra)
     print(f"{len(a.images)} images {tuple(x.shape[-2:])} -> {a.out}")
     return 0
 
