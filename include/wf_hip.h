@@ -614,6 +614,30 @@ int wf_warp_splat(const float* image, const float* depth, const double* geometry
 size_t wf_crack_fill_workspace_bytes(int n, int H, int W);
 int wf_crack_fill(const void* img, const void* mask, const float* depth, void* out_img, void* out_mask, float* out_depth, int n, int H,
                   int W, int min_neighbors, int min_valid_neighbors, int num_segments, void* workspace, void* stream);
+/* The same filling with the two parameters that run_warp.py ships and wf_crack_fill fixes: neighbor_radius 1..4 (the outlier test counts
+ * the pixels of the pixel's OWN segment in the (2 r + 1)^2 window, centre included, BORDER_REFLECT_101, utils_warp.py:577-588) and
+ * num_segments 1..16.  Everything after the outlier test is 3 x 3 as in wf_crack_fill; at (radius 1, <= 5 segments) the two agree bit for
+ * bit.  Refused: H <= radius or W <= radius (reflect-101 is undefined there), a radius or a segment count out of range.  The per-segment
+ * depth sums that order the merge are reduced in a fixed tree (no floating-point atomics).  workspace:
+ * wf_crack_fill_ex_workspace_bytes(n, H, W) bytes, no initialisation needed. */
+size_t wf_crack_fill_ex_workspace_bytes(int n, int H, int W);
+int wf_crack_fill_ex(const void* img, const void* mask, const float* depth, void* out_img, void* out_mask, float* out_depth, int n, int H,
+                     int W, int min_neighbors, int min_valid_neighbors, int num_segments, int neighbor_radius, void* workspace,
+                     void* stream);
+
+/* The confidence filter of warp_single_img (vggt/modules/utils_warp.py:784-808).
+ * wf_select_pair_f32: exact selection on n fp32 values (device): out = 12 device bytes {the k-th smallest (0-based), the min(k + 1, n - 1)-th
+ * smallest, the number of NaNs as a u32}; a NaN sorts last, as in numpy.  Radix select on a monotone unsigned key with integer
+ * histograms: the same input gives the same bits.  The host turns the pair into np.percentile's "linear" threshold.
+ * wf_depth_conf_filter: depth, conf f32 [n] -> out_depth f32 [n] and out_stats = 2 device doubles {mean, count} of the pixels the
+ * reference averages; the mean is a fixed-order fp64 reduction (NaN when the count is 0).  mode 0: out = conf > threshold ? depth : NaN,
+ * mean over the kept non-NaN depths (<= 0 included, as np.nanmean); mode 1 (conf_threshold == 1.0): out = depth, mean over the depths
+ * that are not NaN and > 0; mode 2 (no confidence map, conf may be NULL): out = NaN unless the depth is not NaN and > 0, mean over those. */
+size_t wf_select_pair_f32_workspace_bytes(void);
+int wf_select_pair_f32(const float* x, int64_t n, int64_t k, void* out, void* workspace, void* stream);
+size_t wf_depth_conf_filter_workspace_bytes(void);
+int wf_depth_conf_filter(const float* depth, const float* conf, float threshold, int mode, float* out_depth, double* out_stats, int64_t n,
+                         void* workspace, void* stream);
 
 /* fill_small_cracks in full (vggt/modules/utils_warp.py:386-455) -- what warp_single_img runs INSTEAD of the depth-aware filling for a view
  * with <= 100 splatted depths (:957-962, 973-981): step 1 = 3 x 3 closing + mean of the valid 8-neighbours (>= min_valid_neighbors of them);

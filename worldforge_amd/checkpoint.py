@@ -419,6 +419,54 @@ def audit(path: str) -> dict:
     return {"path": path, "components": comps, "ok": ok}
 
 
+def audit_vggt(folder: str, depth: bool = True) -> dict:
+    """vggt.VGGT.from_pretrained(folder, depth=depth)'s header check as a report of the same form as `audit` (headers and config.json only,
+    no GPU): the one component is `vggt`; the heads this engine does not run (point, track) are noted, not counted."""
+    from .vggt import VGGTConfig, consumed_header, expected_state_dict
+    if not os.path.isdir(folder):
+        raise FileNotFoundError(f"checkpoint folder does not exist: {folder}")
+    c = _component("VGGT", folder)
+    cfg = None
+    cj = os.path.join(folder, "config.json")
+    if os.path.exists(cj):
+        d = _read_json(cj, c)
+        if d is not None:
+            try:
+                cfg = VGGTConfig.from_dict(d)
+                if depth:
+                    cfg.check_depth_layers()
+            except (NotImplementedError, ValueError, TypeError, KeyError) as e:
+                c["refused"].append(str(e))
+    else:
+        c["notes"].append("config.json is absent: the released configuration is assumed")
+        cfg = VGGTConfig()
+    path = os.path.join(folder, "model.safetensors")
+    found = None
+    if not os.path.exists(path):
+        c["missing"].append("model.safetensors")
+    else:
+        try:
+            found, _ = read_header(path)
+        except (ValueError, KeyError, json.JSONDecodeError, OSError) as e:
+            c["notes"].append(f"unreadable: {e}")
+            c["missing"].append("model.safetensors")
+    if found is not None:
+        for e in found.values():
+            c["dtypes"][e["dtype"]] = c["dtypes"].get(e["dtype"], 0) + 1
+            c["bytes"] += int(e["data_offsets"][1] - e["data_offsets"][0])
+        if cfg is not None and not c["refused"]:
+            shapes = {k: {"shape": tuple(int(v) for v in e["shape"])} for k, e in found.items()}
+            import warnings
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", UserWarning)  # (the loader's one warning is the note below)
+                keep = consumed_header(shapes, folder, depth)
+            if len(keep) < len(shapes):
+                c["notes"].append(f"{len(shapes) - len(keep)} tensors of heads this engine does not run are ignored")
+            c["missing"], c["unexpected"], c["wrong_shape"] = compare_header(keep, expected_state_dict(cfg, depth))
+    ok = not (c["missing"] or c["unexpected"] or c["wrong_shape"] or c["refused"])
+    return {"path": folder, "components": {"vggt": c}, "ok": ok}
+
+
 def format_report(rep: dict, limit: int = 10) -> str:
     """The text report: per component the counts and at most `limit` names per class."""
     lines = [f"checkpoint {rep['path']}: {'OK' if rep['ok'] else 'PROBLEMS'}"]
@@ -450,8 +498,9 @@ def main(argv=None) -> int:
                                  description="Audit a checkpoint folder against this engine's loaders (headers and JSON only, no GPU)")
     ap.add_argument("path")
     ap.add_argument("--json", action="store_true", help="print the report as JSON")
+    ap.add_argument("--vggt", action="store_true", help="the folder is a VGGT checkpoint (model.safetensors with the depth head), as run_warp takes it")
     a = ap.parse_args(argv)
-    rep = audit(a.path)
+    rep = audit_vggt(a.path, depth=True) if a.vggt else audit(a.path)
     print(json.dumps(rep, indent=1) if a.json else format_report(rep))
     return 0 if rep["ok"] else 1
 

@@ -503,3 +503,595 @@ extern "C" int wf_crack_fill(const void* img, const void* mask, const float* dep
   WF_LAUNCH_CHECK("wf_crack_fill");
   return WF_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// wf_crack_fill_ex: the same filling with the outlier window radius (1..4) and the number of depth segments (1..16) as parameters -- what
+// run_warp.py ships is radius 3 (7 x 7, centre included), 8 segments, min_neighbors 10, so that nearly every segment loses an outlier and
+// the closing runs for every segment on every pixel.  Workgroups own 64 x 16 tiles:
+//   k_cfx_outlier   stages the tile's segment ids + an r-pixel halo (reflect-101 applied while staging) in LDS and counts from there
+//   k_cfx_fillmask  stages "held by segment s" as one bit per segment (u16) + a 2-pixel halo; dilation = OR, erosion = AND over the
+//                   in-image 3 x 3, for all segments at once; the 8-neighbour count runs only for the bits that survive.  The
+//                   per-segment depth sums (they order the merge) leave the block as ONE partial per segment, reduced in a fixed order
+//   k_cfx_order     sums the partials of a view in a fixed tree and sorts the segments: no floating-point atomics, the same input gives
+//                   the same order on every run
+//   k_cfx_merge     as k_cf_merge, walking the sorted list
+// Everything after the outlier test stays 3 x 3, as in the reference.
+// ------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int XSEG = 16;  // segments of the _ex entry point: the fill set is a u16
+constexpr int XR = 4;     // largest outlier radius
+constexpr int TW = 64, TH = 16, XT = 256;  // tile and workgroup: thread t owns column t % 64 of rows t / 64 + 4 j
+
+struct CXArgs {
+  const uint8_t* img;
+  const uint8_t* mask;
+  const float* depth;
+  uint8_t* out_img;
+  uint8_t* out_mask;
+  float* out_depth;
+  uint8_t* seg;        // [n, H, W] plain segment ids, 255 = not valid
+  uint8_t* segc;       // [n, H, W] the same with the outliers marked (s | 64)
+  uint16_t* fill;      // [n, H, W] bit s = filled by segment s
+  unsigned* stats;     // [n][4] as CFArgs
+  unsigned* segflag;   // [n] bit s = segment s has outliers
+  double* part_sum;    // [n][tiles][XSEG] depth sum of a tile
+  unsigned* part_cnt;  // [n][tiles][XSEG]
+  int* order;          // [n][XSEG + 1]: the covering segments nearest first, [XSEG] = how many
+  int n, H, W, tiles_x, tiles_y;
+  int min_neighbors, min_valid_neighbors, num_segments, radius;
+};
+
+__global__ void k_cfx_init(CXArgs a) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= a.n) return;
+  a.stats[f * 4 + 0] = 0xffffffffu;
+  a.stats[f * 4 + 1] = 0u;
+  a.stats[f * 4 + 2] = 0u;
+  a.stats[f * 4 + 3] = 0u;
+  a.segflag[f] = 0u;
+}
+
+// k_cf_stats with one set of atomics per workgroup instead of per wave, on a grid of at most XSTAT_BLOCKS workgroups a view: the four
+// words of a view are shared by every workgroup that works on it, and the atomics on them serialise
+constexpr int XSTAT_BLOCKS = 120;
+
+__global__ void __launch_bounds__(XT) k_cfx_stats(CXArgs a) {
+  __shared__ unsigned red[4][XT / 64];
+  const int f = blockIdx.y;
+  const size_t np = (size_t)a.H * a.W;
+  unsigned lo = 0xffffffffu, hi = 0u, cnt = 0u, nv = 0u;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < np; i += (size_t)gridDim.x * blockDim.x) {
+    const float d = a.depth[f * np + i];
+    const bool nn = d == d;
+    cnt += nn;
+    if (a.mask[f * np + i] && nn) {
+      const unsigned o = ordered(d);
+      lo = min(lo, o);
+      hi = max(hi, o);
+      ++nv;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = min(lo, (unsigned)__shfl_xor((int)lo, o, 64));
+    hi = max(hi, (unsigned)__shfl_xor((int)hi, o, 64));
+    cnt += (unsigned)__shfl_xor((int)cnt, o, 64);
+    nv += (unsigned)__shfl_xor((int)nv, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    const int w = threadIdx.x >> 6;
+    red[0][w] = lo;
+    red[1][w] = hi;
+    red[2][w] = cnt;
+    red[3][w] = nv;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicMin(a.stats + f * 4 + 0, min(min(red[0][0], red[0][1]), min(red[0][2], red[0][3])));
+    atomicMax(a.stats + f * 4 + 1, max(max(red[1][0], red[1][1]), max(red[1][2], red[1][3])));
+    atomicAdd(a.stats + f * 4 + 2, red[2][0] + red[2][1] + red[2][2] + red[2][3]);
+    atomicAdd(a.stats + f * 4 + 3, red[3][0] + red[3][1] + red[3][2] + red[3][3]);
+  }
+}
+
+__global__ void __launch_bounds__(XT) k_cfx_outlier(CXArgs a) {
+  __shared__ uint8_t t[TH + 2 * XR][TW + 2 * XR + 8];
+  __shared__ unsigned flag;
+  const int f = blockIdx.z;
+  if (a.stats[f * 4 + 3] == 0) return;
+  const int r = a.radius, x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+  const size_t np = (size_t)a.H * a.W;
+  const uint8_t* sg = a.seg + f * np;
+  if (threadIdx.x == 0) flag = 0u;
+  const int tw = TW + 2 * r, th = TH + 2 * r;
+  for (int i = threadIdx.x; i < tw * th; i += XT) {
+    const int ly = i / tw, lx = i % tw;
+    const int gy = y0 + ly - r, gx = x0 + lx - r;
+    uint8_t v = 255;  // beyond the reflected border: never read by a pixel of the image (H > r and W > r keep one reflection enough)
+    if (gy >= -r && gy < a.H + r && gx >= -r && gx < a.W + r) v = sg[(size_t)refl101(gy, a.H) * a.W + refl101(gx, a.W)];
+    t[ly][lx] = v;
+  }
+  __syncthreads();
+  const int lx = threadIdx.x & (TW - 1), x = x0 + lx;
+  unsigned bits = 0u;
+  if (x < a.W)
+    for (int j = 0; j < TH / 4; ++j) {
+      const int ly = (threadIdx.x >> 6) + 4 * j, y = y0 + ly;
+      if (y >= a.H) break;
+      const uint8_t s = t[ly + r][lx + r];
+      uint8_t o = s;
+      if (s != 255) {
+        int c = 0;
+        for (int dy = 0; dy <= 2 * r; ++dy)
+          for (int dx = 0; dx <= 2 * r; ++dx) c += t[ly + dy][lx + dx] == s;
+        if (c < a.min_neighbors) {
+          o = s | 64;
+          bits |= 1u << s;
+        }
+      }
+      a.segc[f * np + (size_t)y * a.W + x] = o;
+    }
+  if (bits) atomicOr(&flag, bits);
+  __syncthreads();
+  if (threadIdx.x == 0 && flag) atomicOr(a.segflag + f, flag);
+}
+
+__global__ void __launch_bounds__(XT) k_cfx_fillmask(CXArgs a) {
+  __shared__ uint16_t held[TH + 4][TW + 4 + 4];  // tile + 2: bit s = the pixel is held by segment s; 0 outside the image
+  __shared__ uint16_t dil[TH + 2][TW + 2 + 2];   // tile + 1: 3 x 3 dilation; all ones outside the image (the erosion ignores the border)
+  __shared__ double wsum[XT / 64];
+  __shared__ unsigned wcnt[XT / 64];
+  __shared__ unsigned present;
+  const int f = blockIdx.z;
+  if (a.stats[f * 4 + 3] == 0) return;
+  const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+  const size_t np = (size_t)a.H * a.W;
+  const uint8_t* sg = a.segc + f * np;
+  const float* dp = a.depth + f * np;
+  const unsigned flags = a.segflag[f];
+  if (threadIdx.x == 0) present = 0u;
+  for (int i = threadIdx.x; i < (TH + 4) * (TW + 4); i += XT) {
+    const int ly = i / (TW + 4), lx = i % (TW + 4);
+    const int gy = y0 + ly - 2, gx = x0 + lx - 2;
+    uint16_t v = 0;
+    if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
+      const uint8_t s = sg[(size_t)gy * a.W + gx];
+      if (s < XSEG) v = (uint16_t)(1u << s);  // 255 = invalid, s | 64 = outlier: neither is held
+    }
+    held[ly][lx] = v;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < (TH + 2) * (TW + 2); i += XT) {
+    const int ly = i / (TW + 2), lx = i % (TW + 2);
+    const int gy = y0 + ly - 1, gx = x0 + lx - 1;
+    unsigned v = 0xffffu;
+    if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
+      v = 0u;
+      for (int dy = 0; dy < 3; ++dy)
+        for (int dx = 0; dx < 3; ++dx) v |= held[ly + dy][lx + dx];
+    }
+    dil[ly][lx] = (uint16_t)v;
+  }
+  __syncthreads();
+  const int lx = threadIdx.x & (TW - 1), x = x0 + lx;
+  int hs[TH / 4];
+  unsigned fm[TH / 4];
+  float dv[TH / 4], ev[TH / 4];
+  unsigned mine = 0u;
+  for (int j = 0; j < TH / 4; ++j) {
+    const int ly = (threadIdx.x >> 6) + 4 * j, y = y0 + ly;
+    hs[j] = -1;
+    fm[j] = 0u;
+    dv[j] = 0.f;
+    ev[j] = 0.f;
+    if (x >= a.W || y >= a.H) continue;
+    const unsigned h = held[ly + 2][lx + 2];
+    unsigned closed = 0xffffu;
+    for (int dy = 0; dy < 3; ++dy)
+      for (int dx = 0; dx < 3; ++dx) closed &= dil[ly + dy][lx + dx];
+    unsigned cand = closed & ~h & flags, got = 0u;
+    while (cand) {  // the bits that survive the closing: count the segment's 8-neighbours (reflect 101)
+      const int s = __ffs(cand) - 1;
+      cand &= cand - 1;
+      int c = 0;
+      for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx)
+          if (dy || dx) c += (held[refl101(y + dy, a.H) - y0 + 2][refl101(x + dx, a.W) - x0 + 2] >> s) & 1;
+      if (c >= a.min_valid_neighbors) got |= 1u << s;
+    }
+    const size_t i = (size_t)y * a.W + x;
+    a.fill[f * np + i] = (uint16_t)got;
+    fm[j] = got;
+    if (h) {
+      hs[j] = __ffs(h) - 1;
+      dv[j] = dp[i];
+    }
+    if (got) ev[j] = est_depth(dp, y, x, a.H, a.W);
+    mine |= h | got;
+  }
+  if (mine) atomicOr(&present, mine);
+  __syncthreads();
+  const unsigned pres = present;
+  const size_t tile = ((size_t)f * a.tiles_y + blockIdx.y) * a.tiles_x + blockIdx.x;
+  for (int s = 0; s < XSEG; ++s) {
+    if (!((pres >> s) & 1u)) {
+      if (threadIdx.x == 0) {
+        a.part_sum[tile * XSEG + s] = 0.0;
+        a.part_cnt[tile * XSEG + s] = 0u;
+      }
+      continue;
+    }
+    double v = 0.0;
+    unsigned c = 0u;
+    for (int j = 0; j < TH / 4; ++j) {
+      if (hs[j] == s) {
+        v += (double)dv[j];
+        ++c;
+      }
+      if ((fm[j] >> s) & 1u) {
+        v += (double)ev[j];
+        ++c;
+      }
+    }
+    v = wave_sum_d(v);
+    for (int o = 32; o > 0; o >>= 1) c += (unsigned)__shfl_xor((int)c, o, 64);
+    if ((threadIdx.x & 63) == 0) {
+      wsum[threadIdx.x >> 6] = v;
+      wcnt[threadIdx.x >> 6] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      a.part_sum[tile * XSEG + s] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+      a.part_cnt[tile * XSEG + s] = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+    }
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(XT) k_cfx_order(CXArgs a) {
+  __shared__ double ss[XT];
+  __shared__ unsigned cc[XT];
+  __shared__ double avg[XSEG];
+  __shared__ unsigned cnt[XSEG];
+  const int f = blockIdx.x, tid = threadIdx.x;
+  int* ord = a.order + f * (XSEG + 1);
+  if (a.stats[f * 4 + 3] == 0) {
+    if (tid == 0) ord[XSEG] = 0;
+    return;
+  }
+  const size_t nt = (size_t)a.tiles_x * a.tiles_y;
+  for (int s = 0; s < a.num_segments; ++s) {
+    double v = 0.0;
+    unsigned c = 0u;
+    for (size_t b = tid; b < nt; b += XT) {
+      v += a.part_sum[(f * nt + b) * XSEG + s];
+      c += a.part_cnt[(f * nt + b) * XSEG + s];
+    }
+    ss[tid] = v;
+    cc[tid] = c;
+    __syncthreads();
+    for (int o = XT / 2; o > 0; o >>= 1) {
+      if (tid < o) {
+        ss[tid] += ss[tid + o];
+        cc[tid] += cc[tid + o];
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      cnt[s] = cc[0];
+      avg[s] = cc[0] > 0 ? (double)(float)(ss[0] / (double)cc[0]) : 1e300;
+    }
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  // far-to-near merge, the LAST writer (nearest) wins -> ascending mean depth, ties keep the later segment first (as k_cf_merge)
+  int order[XSEG], m = 0;
+  for (int s = 0; s < a.num_segments; ++s)
+    if (cnt[s] > 0) order[m++] = s;
+  for (int i = 1; i < m; ++i)
+    for (int j = i; j > 0 && (avg[order[j]] < avg[order[j - 1]] || (avg[order[j]] == avg[order[j - 1]] && order[j] > order[j - 1])); --j) {
+      const int t = order[j];
+      order[j] = order[j - 1];
+      order[j - 1] = t;
+    }
+  for (int i = 0; i < m; ++i) ord[i] = order[i];
+  ord[XSEG] = m;
+}
+
+__global__ void k_cfx_merge(CXArgs a) {
+  const int f = blockIdx.y;
+  const size_t np = (size_t)a.H * a.W;
+  const uint8_t* sg = a.segc + f * np;
+  const uint8_t* im = a.img + f * np * 3;
+  const float* dp = a.depth + f * np;
+  const int* ord = a.order + f * (XSEG + 1);
+  const int m = ord[XSEG];
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < np; i += (size_t)gridDim.x * blockDim.x) {
+    const int y = (int)(i / a.W), x = (int)(i % a.W);
+    uint8_t r = 0, g = 0, b = 0, mk = 0;
+    float d = __uint_as_float(0x7fc00000u);
+    if (m > 0) {
+      const unsigned own = sg[i], fm = a.fill[f * np + i];
+      for (int k = 0; k < m; ++k) {
+        const int s = ord[k];
+        if (own == (unsigned)s) {
+          r = im[i * 3];
+          g = im[i * 3 + 1];
+          b = im[i * 3 + 2];
+          d = dp[i];
+          mk = 1;
+          break;
+        }
+        if ((fm >> s) & 1u) {
+          float acc[3] = {0.f, 0.f, 0.f}, c = 0.f;
+          for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) {
+              if (!dy && !dx) continue;
+              const size_t q = (size_t)refl101(y + dy, a.H) * a.W + refl101(x + dx, a.W);
+              if (sg[q] == (uint8_t)s) {
+                acc[0] += (float)im[q * 3] / 255.0f;
+                acc[1] += (float)im[q * 3 + 1] / 255.0f;
+                acc[2] += (float)im[q * 3 + 2] / 255.0f;
+                c += 1.f;
+              }
+            }
+          const float sc = fmaxf(c, 1e-6f);
+          r = (uint8_t)(int)(acc[0] / sc * 255.0f);
+          g = (uint8_t)(int)(acc[1] / sc * 255.0f);
+          b = (uint8_t)(int)(acc[2] / sc * 255.0f);
+          d = est_depth(dp, y, x, a.H, a.W);
+          mk = 1;
+          break;
+        }
+      }
+    }
+    a.out_img[(f * np + i) * 3] = r;
+    a.out_img[(f * np + i) * 3 + 1] = g;
+    a.out_img[(f * np + i) * 3 + 2] = b;
+    a.out_mask[f * np + i] = mk;
+    a.out_depth[f * np + i] = d;
+  }
+}
+
+struct CXLayout {
+  size_t seg, segc, fill, part_sum, part_cnt, order, stats, segflag, total;
+  int tiles_x, tiles_y;
+};
+inline CXLayout cx_layout(int n, int H, int W) {
+  CXLayout l;
+  l.tiles_x = (W + TW - 1) / TW;
+  l.tiles_y = (H + TH - 1) / TH;
+  const size_t np = (size_t)n * H * W, nt = (size_t)n * l.tiles_x * l.tiles_y;
+  auto up = [](size_t v) { return (v + 63) / 64 * 64; };
+  l.seg = 0;
+  l.segc = up(np);
+  l.fill = l.segc + up(np);
+  l.part_sum = l.fill + up(2 * np);
+  l.part_cnt = l.part_sum + up(nt * XSEG * sizeof(double));
+  l.order = l.part_cnt + up(nt * XSEG * sizeof(unsigned));
+  l.stats = l.order + up((size_t)n * (XSEG + 1) * sizeof(int));
+  l.segflag = l.stats + up((size_t)n * 4 * sizeof(unsigned));
+  l.total = l.segflag + up((size_t)n * sizeof(unsigned));
+  return l;
+}
+
+}  // namespace
+
+extern "C" size_t wf_crack_fill_ex_workspace_bytes(int n, int H, int W) {
+  if (n <= 0 || H <= 0 || W <= 0) return 0;
+  return cx_layout(n, H, W).total;
+}
+
+extern "C" int wf_crack_fill_ex(const void* img, const void* mask, const float* depth, void* out_img, void* out_mask, float* out_depth, int n,
+                                int H, int W, int min_neighbors, int min_valid_neighbors, int num_segments, int neighbor_radius,
+                                void* workspace, void* stream) {
+  WF_CHECK_ARG(img && mask && depth && out_img && out_mask && out_depth && workspace, "wf_crack_fill_ex: null pointer");
+  WF_CHECK_ARG(neighbor_radius >= 1 && neighbor_radius <= XR, "wf_crack_fill_ex: neighbor_radius (%d) must be 1..%d", neighbor_radius, XR);
+  WF_CHECK_ARG(num_segments >= 1 && num_segments <= XSEG, "wf_crack_fill_ex: num_segments (%d) must be 1..%d", num_segments, XSEG);
+  WF_CHECK_ARG(n > 0 && n <= 65535 && H >= 2 && W >= 2 && (size_t)H * W < (1u << 31), "wf_crack_fill_ex: bad sizes n=%d H=%d W=%d", n, H, W);
+  WF_CHECK_ARG(H > neighbor_radius && W > neighbor_radius,
+               "wf_crack_fill_ex: H=%d W=%d must exceed neighbor_radius=%d (BORDER_REFLECT_101 is undefined otherwise)", H, W, neighbor_radius);
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)workspace;
+  const CXLayout l = cx_layout(n, H, W);
+  WF_CHECK_ARG(l.tiles_y <= 65535, "wf_crack_fill_ex: H=%d is too large", H);
+  CXArgs a;
+  a.img = (const uint8_t*)img; a.mask = (const uint8_t*)mask; a.depth = depth;
+  a.out_img = (uint8_t*)out_img; a.out_mask = (uint8_t*)out_mask; a.out_depth = out_depth;
+  a.seg = ws + l.seg; a.segc = ws + l.segc; a.fill = (uint16_t*)(ws + l.fill);
+  a.part_sum = (double*)(ws + l.part_sum); a.part_cnt = (unsigned*)(ws + l.part_cnt); a.order = (int*)(ws + l.order);
+  a.stats = (unsigned*)(ws + l.stats); a.segflag = (unsigned*)(ws + l.segflag);
+  a.n = n; a.H = H; a.W = W; a.tiles_x = l.tiles_x; a.tiles_y = l.tiles_y;
+  a.min_neighbors = min_neighbors; a.min_valid_neighbors = min_valid_neighbors; a.num_segments = num_segments; a.radius = neighbor_radius;
+  CFArgs b = {};  // the segment ids are the 3 x 3 path's kernel: they do not depend on the window
+  b.mask = a.mask; b.depth = depth; b.seg = a.seg; b.stats = a.stats; b.n = n; b.H = H; b.W = W; b.num_segments = num_segments;
+  const dim3 sgrid((unsigned)std::min<size_t>(((size_t)H * W + 2047) / 2048, XSTAT_BLOCKS), (unsigned)n);
+  const dim3 lin((unsigned)std::min<size_t>(((size_t)H * W + 255) / 256, 1024), (unsigned)n), blk(256);
+  const dim3 tiles((unsigned)l.tiles_x, (unsigned)l.tiles_y, (unsigned)n);
+  hipLaunchKernelGGL(k_cfx_init, dim3((unsigned)((n + 255) / 256)), blk, 0, st, a);
+  hipLaunchKernelGGL(k_cfx_stats, sgrid, dim3(XT), 0, st, a);
+  hipLaunchKernelGGL(k_cf_segid, lin, blk, 0, st, b);
+  hipLaunchKernelGGL(k_cfx_outlier, tiles, dim3(XT), 0, st, a);
+  hipLaunchKernelGGL(k_cfx_fillmask, tiles, dim3(XT), 0, st, a);
+  hipLaunchKernelGGL(k_cfx_order, dim3((unsigned)n), dim3(XT), 0, st, a);
+  hipLaunchKernelGGL(k_cfx_merge, lin, blk, 0, st, a);
+  WF_LAUNCH_CHECK("wf_crack_fill_ex");
+  return WF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The confidence filter of warp_single_img (utils_warp.py:784-808): np.percentile(conf, q) needs the k-th and (k + 1)-th smallest of the
+// confidence map -- an exact radix select on the monotone key of ordered(), four 8-bit digits, integer histograms only (the same input
+// gives the same bits; ties, the normal case for 1 + exp(x), cost nothing) -- and the filter itself is one pass with a fixed-order fp64 mean.
+// ------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct SelArgs {
+  const float* x;
+  size_t n;
+  unsigned* hist;   // [4 passes][2 ranks][256]
+  unsigned* state;  // [0..1] key prefix of rank j, [2..3] rank left inside the prefix, [4] NaN count
+  float* out;       // {k-th, (k+1)-th smallest (NaN sorts last, as numpy), NaN count as u32 bits}
+};
+
+__device__ __forceinline__ unsigned sel_key(float v) { return v == v ? ordered(v) : 0xffffffffu; }
+
+__global__ void k_sel_init(SelArgs a, unsigned k0, unsigned k1) {  // (the memset before it zeroed the histograms, prefixes and the NaN count)
+  if (threadIdx.x == 0) {
+    a.state[2] = k0;
+    a.state[3] = k1;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_sel_hist(SelArgs a, int pass) {
+  __shared__ unsigned h[2][256];
+  h[0][threadIdx.x] = 0u;
+  h[1][threadIdx.x] = 0u;
+  __syncthreads();
+  const int shift = 24 - 8 * pass;
+  const unsigned p0 = a.state[0], p1 = a.state[1];
+  unsigned nan = 0u;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (size_t)gridDim.x * blockDim.x) {
+    const float v = a.x[i];
+    const unsigned key = sel_key(v);
+    const unsigned d = (key >> shift) & 255u;
+    if (pass == 0) {
+      nan += v != v;
+      atomicAdd(&h[0][d], 1u);
+      atomicAdd(&h[1][d], 1u);
+    } else {
+      const unsigned hi = key >> (shift + 8);
+      if (hi == (p0 >> (shift + 8))) atomicAdd(&h[0][d], 1u);
+      if (hi == (p1 >> (shift + 8))) atomicAdd(&h[1][d], 1u);
+    }
+  }
+  __syncthreads();
+  unsigned* g = a.hist + (size_t)pass * 512;
+  if (h[0][threadIdx.x]) atomicAdd(g + threadIdx.x, h[0][threadIdx.x]);
+  if (h[1][threadIdx.x]) atomicAdd(g + 256 + threadIdx.x, h[1][threadIdx.x]);
+  if (pass == 0 && nan) atomicAdd(a.state + 4, nan);
+}
+
+__global__ void k_sel_scan(SelArgs a, int pass) {  // two lanes, one per rank: 256 bins
+  const int j = threadIdx.x;
+  if (j < 2) {
+    const unsigned* g = a.hist + (size_t)pass * 512 + j * 256;
+    unsigned k = a.state[2 + j], b = 0u;
+    for (; b < 255u; ++b) {
+      const unsigned c = g[b];
+      if (k < c) break;
+      k -= c;
+    }
+    const unsigned prefix = a.state[j] | (b << (24 - 8 * pass));
+    a.state[j] = prefix;
+    a.state[2 + j] = k;
+    if (pass == 3) a.out[j] = prefix == 0xffffffffu ? __uint_as_float(0x7fc00000u) : unordered(prefix);
+  }
+  if (pass == 3 && j == 2) a.out[2] = __uint_as_float(a.state[4]);
+}
+
+constexpr int DCF_BLOCKS = 1024;
+
+__global__ void __launch_bounds__(256) k_dcf(const float* depth, const float* conf, float thr, int mode, float* out, double* psum,
+                                             unsigned* pcnt, size_t n) {
+  __shared__ double ws[4];
+  __shared__ unsigned wc[4];
+  double s = 0.0;
+  unsigned c = 0u;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float d = depth[i];
+    bool keep, mean;
+    if (mode == 0) {         // conf > threshold; nanmean of the kept depths (<= 0 included)
+      keep = conf[i] > thr;
+      mean = keep && d == d;
+    } else if (mode == 1) {  // conf_threshold == 1.0: the map passes through, the mean runs over the valid depths
+      keep = true;
+      mean = d == d && d > 0.f;
+    } else {                 // no confidence map: the invalid depths become NaN
+      keep = d == d && d > 0.f;
+      mean = keep;
+    }
+    out[i] = keep ? d : __uint_as_float(0x7fc00000u);
+    if (mean) {
+      s += (double)d;
+      ++c;
+    }
+  }
+  s = wave_sum_d(s);
+  for (int o = 32; o > 0; o >>= 1) c += (unsigned)__shfl_xor((int)c, o, 64);
+  if ((threadIdx.x & 63) == 0) {
+    ws[threadIdx.x >> 6] = s;
+    wc[threadIdx.x >> 6] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    psum[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+    pcnt[blockIdx.x] = (wc[0] + wc[1]) + (wc[2] + wc[3]);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_dcf_final(const double* psum, const unsigned* pcnt, int nb, double* stats) {
+  __shared__ double ss[256];
+  __shared__ unsigned long long cc[256];
+  double v = 0.0;
+  unsigned long long c = 0;
+  for (int b = threadIdx.x; b < nb; b += 256) {
+    v += psum[b];
+    c += pcnt[b];
+  }
+  ss[threadIdx.x] = v;
+  cc[threadIdx.x] = c;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      ss[threadIdx.x] += ss[threadIdx.x + o];
+      cc[threadIdx.x] += cc[threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    stats[0] = cc[0] ? ss[0] / (double)cc[0] : (double)__uint_as_float(0x7fc00000u);
+    stats[1] = (double)cc[0];
+  }
+}
+
+}  // namespace
+
+extern "C" size_t wf_select_pair_f32_workspace_bytes(void) { return (4 * 2 * 256 + 16) * sizeof(unsigned); }
+
+extern "C" int wf_select_pair_f32(const float* x, int64_t n, int64_t k, void* out, void* workspace, void* stream) {
+  WF_CHECK_ARG(x && out && workspace, "wf_select_pair_f32: null pointer");
+  WF_CHECK_ARG(n >= 1 && n < ((int64_t)1 << 32) - 1, "wf_select_pair_f32: n=%lld must be 1..2^32-2", (long long)n);
+  WF_CHECK_ARG(k >= 0 && k < n, "wf_select_pair_f32: k=%lld must be 0..n-1", (long long)k);
+  hipStream_t st = (hipStream_t)stream;
+  SelArgs a;
+  a.x = x; a.n = (size_t)n; a.hist = (unsigned*)workspace; a.state = a.hist + 4 * 2 * 256; a.out = (float*)out;
+  if (hipMemsetAsync(a.hist, 0, wf_select_pair_f32_workspace_bytes(), st) != hipSuccess)
+    return check_hip(hipGetLastError(), "wf_select_pair_f32: memset");
+  hipLaunchKernelGGL(k_sel_init, dim3(1), dim3(64), 0, st, a, (unsigned)k, (unsigned)std::min<int64_t>(k + 1, n - 1));
+  const dim3 grid((unsigned)std::min<size_t>((a.n + 255) / 256, 1024)), blk(256);
+  for (int pass = 0; pass < 4; ++pass) {
+    hipLaunchKernelGGL(k_sel_hist, grid, blk, 0, st, a, pass);
+    hipLaunchKernelGGL(k_sel_scan, dim3(1), dim3(64), 0, st, a, pass);
+  }
+  WF_LAUNCH_CHECK("wf_select_pair_f32");
+  return WF_OK;
+}
+
+extern "C" size_t wf_depth_conf_filter_workspace_bytes(void) { return DCF_BLOCKS * (sizeof(double) + sizeof(unsigned)); }
+
+extern "C" int wf_depth_conf_filter(const float* depth, const float* conf, float threshold, int mode, float* out_depth, double* out_stats,
+                                    int64_t n, void* workspace, void* stream) {
+  WF_CHECK_ARG(depth && out_depth && out_stats && workspace, "wf_depth_conf_filter: null pointer");
+  WF_CHECK_ARG(mode >= 0 && mode <= 2, "wf_depth_conf_filter: mode=%d must be 0 (conf > threshold), 1 (pass through) or 2 (valid depths)", mode);
+  WF_CHECK_ARG(mode != 0 || conf, "wf_depth_conf_filter: mode 0 needs the confidence map");
+  WF_CHECK_ARG(n >= 1 && n < ((int64_t)1 << 40), "wf_depth_conf_filter: bad n=%lld", (long long)n);
+  hipStream_t st = (hipStream_t)stream;
+  double* psum = (double*)workspace;
+  unsigned* pcnt = (unsigned*)(psum + DCF_BLOCKS);
+  const int nb = (int)std::min<size_t>(((size_t)n + 255) / 256, DCF_BLOCKS);  // a function of n alone: the reduction order is fixed
+  hipLaunchKernelGGL(k_dcf, dim3((unsigned)nb), dim3(256), 0, st, depth, conf, threshold, mode, out_depth, psum, pcnt, (size_t)n);
+  hipLaunchKernelGGL(k_dcf_final, dim3(1), dim3(256), 0, st, (const double*)psum, (const unsigned*)pcnt, nb, out_stats);
+  WF_LAUNCH_CHECK("wf_depth_conf_filter");
+  return WF_OK;
+}

@@ -1,8 +1,10 @@
 """Stage-1 depth-guided forward warping on the GPU (vggt/modules/utils_warp.py warp_single_img :724-1001).
 
-`forward_splat` (:863-945) and `crack_fill` (:954-985 -> :386-706) are the tensor-sized parts of the stage-1 warper: one image + depth map
--> n warped views with validity masks (the `warp_*` / `mask_*` frames the guided sampler consumes), cracks closed.  The camera paths
-(:64-383) are 4x4 host math (`camera_path`) and the confidence filter a percentile on the host: both stay with the caller.
+`forward_splat` (:863-945) and `crack_fill` / `crack_fill_ex` (:954-985 -> :386-706) are the tensor-sized parts of the stage-1 warper: one
+image + depth map -> n warped views with validity masks (the `warp_*` / `mask_*` frames the guided sampler consumes), cracks closed.  The
+camera paths (:64-383) are 4x4 host math (`camera_path`); the confidence filter (:774-808) is `depth_conf_filter` (np.percentile's
+threshold from an exact select on the device, the mean in fp64); `warp_single_img` joins them as the reference does, and
+`python -m worldforge_amd.run_warp` is its command line.
 """
 from __future__ import annotations
 
@@ -131,6 +133,13 @@ def crack_fill(images: torch.Tensor, masks: torch.Tensor, depths: torch.Tensor, 
     oi, om, od = torch.empty_like(images), torch.empty_like(masks), torch.empty_like(depths)
     call("wf_crack_fill", images.data_ptr(), masks.data_ptr(), depths.data_ptr(), oi.data_ptr(), om.data_ptr(), od.data_ptr(), n, H, W,
          int(min_neighbors), int(min_valid_neighbors), int(num_segments), ws.data_ptr(), ops.stream())
+    return _route_sparse_views(images, masks, depths, oi, om, od, original_depth, has_depth_conf, depth_threshold, max_crack_size,
+                               min_valid_neighbors)
+
+
+def _route_sparse_views(images, masks, depths, oi, om, od, original_depth, has_depth_conf, depth_threshold, max_crack_size,
+                        min_valid_neighbors):
+    """Views with <= 100 splatted depths take fill_small_cracks instead (utils_warp.py:957-962, 973-981), their depth unchanged."""
     few = (~torch.isnan(depths)).flatten(1).sum(1) <= 100
     if bool(few.any()):  # once per camera path, outside any loop
         for i in torch.nonzero(few).flatten().tolist():
@@ -138,6 +147,181 @@ def crack_fill(images: torch.Tensor, masks: torch.Tensor, depths: torch.Tensor, 
                                             min_valid_neighbors)
             od[i] = depths[i]
     return oi, om, od
+
+
+def crack_fill_ex(images: torch.Tensor, masks: torch.Tensor, depths: torch.Tensor, min_neighbors: int = 4, neighbor_radius: int = 1,
+                  min_valid_neighbors: int = 3, num_segments: int = 5, original_depth: torch.Tensor = None, has_depth_conf: bool = False,
+                  depth_threshold: float = 0.1, max_crack_size: int = 5):
+    """`crack_fill` with the outlier window radius (1..4) and the number of depth segments (1..16) as parameters (wf_crack_fill_ex): what
+    run_warp.py ships is min_neighbors 10 in a 7 x 7 window (radius 3) over 8 segments.  At (radius 1, <= 5 segments) it returns
+    `crack_fill`'s bits."""
+    n, H, W, _ = images.shape
+    assert images.dtype == torch.uint8 and masks.dtype == torch.uint8 and depths.dtype == torch.float32
+    images, masks, depths = images.contiguous(), masks.contiguous(), depths.contiguous()
+    from ._ffi import lib
+    ws = torch.empty(int(lib().wf_crack_fill_ex_workspace_bytes(n, H, W)), dtype=torch.uint8, device=images.device)
+    oi, om, od = torch.empty_like(images), torch.empty_like(masks), torch.empty_like(depths)
+    call("wf_crack_fill_ex", images.data_ptr(), masks.data_ptr(), depths.data_ptr(), oi.data_ptr(), om.data_ptr(), od.data_ptr(), n, H, W,
+         int(min_neighbors), int(min_valid_neighbors), int(num_segments), int(neighbor_radius), ws.data_ptr(), ops.stream())
+    return _route_sparse_views(images, masks, depths, oi, om, od, original_depth, has_depth_conf, depth_threshold, max_crack_size,
+                               min_valid_neighbors)
+
+
+# ---- the confidence filter of warp_single_img (utils_warp.py:774-808) -----------------------------------------------------------------------
+def percentile_plan(n: int, q: float):
+    """Where np.percentile(a, q) (method "linear") looks in the sorted float32 array of n values: (k, gamma) with the result
+    lerp(sorted[k], sorted[min(k + 1, n - 1)], gamma).  numpy divides q by 100 IN THE ARRAY'S DTYPE and multiplies by n - 1 there, so
+    the virtual index and gamma are float32 (numpy/lib/_function_base_impl.py: percentile, _quantile, _get_indexes, _get_gamma)."""
+    q32 = np.float32(q) / np.float32(100)
+    if not (0.0 <= q32 <= 1.0):
+        raise ValueError("Percentiles must be in the range [0, 100]")
+    v = np.float32(n - 1) * q32
+    if v >= n - 1:  # numpy indexes the last element as -1 and takes gamma = v - (-1): both neighbours are the maximum
+        return n - 1, np.float32(np.float64(v) + 1.0)
+    return int(np.floor(v)), np.float32(v - np.floor(v))
+
+
+def lerp_f32(a, b, gamma) -> np.float32:
+    """numpy's _lerp on float32 scalars: a + (b - a) gamma, replaced by b - (b - a) (1 - gamma) where gamma >= 0.5."""
+    a, b, g = np.float32(a), np.float32(b), np.float32(gamma)
+    with np.errstate(invalid="ignore"):  # inf - inf, inf * 0: NaN, as in numpy
+        d = np.float32(b - a)
+        return np.float32(b - d * np.float32(np.float32(1) - g)) if g >= 0.5 else np.float32(a + d * g)
+
+
+def select_pair(x: torch.Tensor, k: int):
+    """wf_select_pair_f32: the k-th and min(k + 1, n - 1)-th smallest of the fp32 device tensor x (exact; a NaN sorts last) and the number
+    of NaNs -> (lo, hi, nan_count) as np.float32, np.float32, int.  One host synchronisation (12 bytes)."""
+    from ._ffi import lib
+    x = x.to(torch.float32).contiguous().flatten()
+    ws = torch.empty(int(lib().wf_select_pair_f32_workspace_bytes()), dtype=torch.uint8, device=x.device)
+    out = torch.empty(3, dtype=torch.float32, device=x.device)
+    call("wf_select_pair_f32", x.data_ptr(), x.numel(), int(k), out.data_ptr(), ws.data_ptr(), ops.stream())
+    h = out.cpu().numpy()
+    return h[0], h[1], int(h[2:3].view(np.uint32)[0])
+
+
+def percentile_f32(x: torch.Tensor, q: float) -> np.float32:
+    """np.percentile(x.flatten(), q) of an fp32 device tensor, bit for bit as an fp32 value; a NaN in x is a ValueError (numpy would return
+    NaN, and a NaN threshold keeps no pixel)."""
+    k, gamma = percentile_plan(x.numel(), q)
+    lo, hi, nans = select_pair(x, k)
+    if nans:
+        raise ValueError(f"percentile_f32: {nans} NaN value(s) in the input (numpy's percentile would be NaN)")
+    return lerp_f32(lo, hi, gamma)
+
+
+def depth_conf_filter(depth: torch.Tensor, depth_conf: torch.Tensor = None, conf_threshold: float = 0.5, threshold=None):
+    """The filter of utils_warp.py:774-808 on the device: depth f32 [H, W], depth_conf f32 [H, W] or None -> (filtered depth f32 [H, W] on
+    the device, threshold (np.float32 or None), mean depth (float: a fixed-order fp64 mean), count).  With a confidence map and
+    conf_threshold != 1.0 the threshold is np.percentile(conf, (1 - conf_threshold) * 100) (or `threshold`, if given), the kept pixels
+    are conf > threshold and the mean runs over their non-NaN depths; with conf_threshold == 1.0 the map passes through and without a map
+    the invalid depths become NaN -- the mean then runs over the depths that are not NaN and > 0.  Two host synchronisations: the
+    selected pair and the (mean, count) pair."""
+    from ._ffi import lib
+    depth = depth.to(torch.float32).contiguous()
+    thr, mode, conf = None, 2, None
+    if depth_conf is not None:
+        conf = depth_conf.to(device=depth.device, dtype=torch.float32).contiguous()
+        if tuple(conf.shape) != tuple(depth.shape):
+            raise ValueError(f"depth_conf {tuple(conf.shape)} does not match depth {tuple(depth.shape)}")
+        mode = 1
+        if conf_threshold != 1.0:
+            thr = np.float32(threshold) if threshold is not None else percentile_f32(conf, (1 - conf_threshold) * 100)
+            mode = 0
+    out = torch.empty_like(depth)
+    stats = torch.empty(2, dtype=torch.float64, device=depth.device)
+    ws = torch.empty(int(lib().wf_depth_conf_filter_workspace_bytes()), dtype=torch.uint8, device=depth.device)
+    call("wf_depth_conf_filter", depth.data_ptr(), conf.data_ptr() if mode == 0 else None, float(thr) if thr is not None else 0.0, mode,
+         out.data_ptr(), stats.data_ptr(), depth.numel(), ws.data_ptr(), ops.stream())
+    mean, count = stats.cpu().tolist()
+    return out, thr, mean, int(count)
+
+
+# ---- warp_single_img (utils_warp.py:724-1001) and the parameters run_warp.py hands it --------------------------------------------------------
+RUN_WARP_DEFAULTS = dict(depth_threshold=0.1, max_crack_size=6, min_valid_neighbors=2, min_neighbors=10, neighbor_radius=3,
+                         skip_outlier_detection=False, use_fast_outlier_detection=True)  # create_default_crack_params(run_warp.py's parser)
+
+
+def crack_params_from_args(args=None) -> dict:
+    """create_default_crack_params (utils_warp.py:707-717), line for line."""
+    return {
+        "depth_threshold": getattr(args, "crack_depth_threshold", 0.1) if args is not None else 0.1,
+        "max_crack_size": getattr(args, "crack_max_size", 5) if args is not None else 5,
+        "min_valid_neighbors": getattr(args, "crack_min_neighbors", 3) if args is not None else 3,
+        "min_neighbors": getattr(args, "outlier_min_neighbors", 4) if args is not None else 4,
+        "neighbor_radius": getattr(args, "outlier_neighbor_radius", 1) if args is not None else 1,
+        "skip_outlier_detection": getattr(args, "skip_outlier_detection", False) if args is not None else False,
+        "use_fast_outlier_detection": getattr(args, "use_fast_outlier_detection", True) if args is not None else True,
+    }
+
+
+def frame_infos(direction: str, degree: float, frame_num: int):
+    """The reference's list of dicts (utils_warp.py:851-856, 991-997).  `angle` is its LABEL degree (i + 1) / frame_num, not the angle of
+    the camera (that is degree i / (frame_num - 1)): the file names are built from it."""
+    out = [{"type": "original", "camera_name": "original", "direction": direction, "angle": 0.0}]
+    for i in range(1, frame_num):
+        angle = degree * (i + 1) / frame_num
+        out.append({"type": "single_view_warped", "direction": direction, "angle": angle, "camera_name": f"{direction}_{angle:.2f}_deg"})
+    return out
+
+
+def warp_single_img(extrinsic, intrinsic, image, depth_map, depth_conf=None, direction="right", degree=15.0, conf_threshold=0.5,
+                    frame_num=24, fill_cracks=True, crack_params=None, look_at_depth=1.0, depth_segments=5, device="cuda:0",
+                    use_backward=False, disable_depth_aware_fill=False):
+    """The reference's warp_single_img on the device.  extrinsic 3x4 / 4x4, intrinsic 3x3 (host); image [3, H, W] (or [1, 3, H, W]) tensor
+    or [H, W, 3] array, float in [0, 1]; depth_map, depth_conf [H, W] (singleton axes are squeezed), host or device.  look_at_depth and
+    depth_segments are the two fields the reference reads from its `args`; crack_params is laid over crack_params_from_args(None).
+    -> (images u8 [frame_num, H, W, 3], masks u8 [frame_num, H, W]) on the device and the reference's list of dicts.  Frame 0 is the
+    source image with a mask of ones.
+    ValueError: a NaN in the confidence map; no pixel left by the filter (the reference goes on with a NaN camera); an image above 1.0
+    (the reference then casts instead of scaling); use_backward, disable_depth_aware_fill, crack_params' skip_outlier_detection or
+    use_fast_outlier_detection=False (run_warp.py's validate_args fixes all four); a radius or segment count wf_crack_fill_ex refuses."""
+    if use_backward or disable_depth_aware_fill:
+        raise ValueError("warp_single_img: use_backward / disable_depth_aware_fill are not implemented (run_warp.py fixes both to False)")
+    params = crack_params_from_args(None)
+    params.update(crack_params or {})
+    if params.get("skip_outlier_detection", False) or not params.get("use_fast_outlier_detection", True):
+        raise ValueError("warp_single_img: skip_outlier_detection and the scipy remove_outliers route (use_fast_outlier_detection=False) "
+                         "are not implemented (run_warp.py fixes them to False / True)")
+    radius, nseg = int(params["neighbor_radius"]), int(depth_segments)
+    if fill_cracks and not (1 <= radius <= 4 and 1 <= nseg <= 16):
+        raise ValueError(f"warp_single_img: neighbor_radius {radius} must be 1..4 and depth_segments {nseg} 1..16")
+    dev = torch.device(device)
+    img = torch.as_tensor(image, dtype=torch.float32)
+    if img.dim() == 4:
+        img = img[0]
+    if img.dim() != 3:
+        raise ValueError(f"image must be [3, H, W] or [H, W, 3], got {tuple(img.shape)}")
+    if isinstance(image, torch.Tensor):
+        img = img.permute(1, 2, 0)
+    if img.shape[2] != 3:
+        raise ValueError(f"image must have 3 channels, got {tuple(img.shape)}")
+    if img.device.type == "cpu" and float(img.max()) > 1.0:  # (a device image is taken at its word: no synchronisation for this)
+        raise ValueError("warp_single_img: the image must be in [0, 1]")
+    img = img.to(dev).contiguous()
+    H, W, _ = img.shape
+    depth = torch.as_tensor(depth_map, dtype=torch.float32).to(dev).squeeze()
+    conf = torch.as_tensor(depth_conf, dtype=torch.float32).to(dev).squeeze() if depth_conf is not None else None
+    if tuple(depth.shape) != (H, W):
+        raise ValueError(f"depth_map {tuple(depth.shape)} does not match the image {(H, W)}")
+    filtered, _, mean, count = depth_conf_filter(depth, conf, conf_threshold)
+    if count == 0:
+        raise ValueError("warp_single_img: no pixel survives the depth / confidence filter")
+    adjusted = float(np.float32(np.float32(mean) * np.float32(look_at_depth)))  # fp32 as the reference's np.float32 * float
+    cams = camera_path(direction, extrinsic, degree, frame_num, adjusted)
+    images = torch.empty((frame_num, H, W, 3), dtype=torch.uint8, device=dev)
+    masks = torch.ones((frame_num, H, W), dtype=torch.uint8, device=dev)
+    images[0] = (img * 255).to(torch.uint8)
+    if frame_num > 1:
+        wi, wm, wd = forward_splat(img, filtered, intrinsic, extrinsic, cams[1:], device=dev)
+        if fill_cracks:
+            wi, wm, _ = crack_fill_ex(wi, wm, wd, min_neighbors=params["min_neighbors"], neighbor_radius=radius,
+                                      min_valid_neighbors=params["min_valid_neighbors"], num_segments=nseg, original_depth=filtered,
+                                      has_depth_conf=conf is not None, depth_threshold=params["depth_threshold"],
+                                      max_crack_size=params["max_crack_size"])
+        images[1:], masks[1:] = wi, wm
+    return images, masks, frame_infos(direction, degree, frame_num)
 
 
 def small_crack_fill(image: torch.Tensor, mask: torch.Tensor, original_depth: torch.Tensor = None, has_depth_conf: bool = False,
