@@ -601,7 +601,8 @@ int wf_ncthw_to_cl_f16(const float* in, float* out_f32, void* out_f16, int C, in
  * nearest source wins (z-buffer).  image f32 [H][W][3] in [0,1]; depth f32 [H][W] (NaN / <= 0 = invalid, i.e. already filtered by
  * confidence); geometry = 30 doubles {K^-1 (9), K (9), R^T (9), -R^T t (3)} of the source camera; cameras = n x 12 doubles (rows of
  * [R | t] of every new camera).  out_images u8 [n][H][W][3], out_masks u8 [n][H][W] (1 = written), out_depth f32 [n][H][W] (NaN =
- * empty); zbuffer: n*H*W 8-byte words of scratch. */
+ * empty); zbuffer: 12 * n*H*W bytes of scratch, 8-byte aligned (a 64-bit depth key and a 32-bit owner word per target pixel).  Where
+ * several sources reach a target pixel with bit-equal z, the one with the lowest raster index y * W + x writes it. */
 int wf_warp_splat(const float* image, const float* depth, const double* geometry, const double* cameras, void* out_images, void* out_masks,
                   float* out_depth, void* zbuffer, int n_cameras, int H, int W, void* stream);
 /* Depth-aware crack filling of the warped views (vggt/modules/utils_warp.py depth_aware_crack_filling :647-691 with segment_depth_map

@@ -1,6 +1,7 @@
 """GPU: stage 1 on the engine -- wf_select_pair_f32 + the host lerp against np.percentile (bit for bit), wf_depth_conf_filter against numpy,
 wf_crack_fill_ex against the CPU restatement of tests/stage1_cases.py (masks, NaN patterns and fill decisions exact, the bars of
-tests/test_gpu_warp.py for depths and colours), warp.warp_single_img against the recorded reference (tests/golden/g28_stage1_*), and
+tests/test_gpu_warp.py for depths and colours; across tile corners and on a view wider than every capped grid with the inputs of
+tests/stage1_edges.py), warp.warp_single_img against the recorded reference (tests/golden/g28_stage1_*), and
 `python -m worldforge_amd.run_warp` end to end on a test-width VGGT checkpoint."""
 import os
 import re
@@ -10,6 +11,7 @@ import pytest
 import torch
 
 from tests import stage1_cases as sc
+from tests import stage1_edges as se
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -225,6 +227,92 @@ def test_crack_fill_ex_at_radius_1_and_5_segments_is_crack_fill_bit_for_bit(H, W
         warp.crack_fill_ex(*dev, num_segments=17)
     with pytest.raises(RuntimeError, match="neighbor_radius"):
         warp.crack_fill_ex(*dev, neighbor_radius=5)
+
+
+# ---- wf_crack_fill_ex / wf_crack_fill across tile corners and beyond one grid (inputs and their conditions: tests/stage1_edges.py) -------------
+@pytest.mark.parametrize("H,W", se.CORNER_SHAPES)
+def test_crack_fill_ex_across_tile_corners(H, W):
+    """3 x 3 ragged tiles, a one-pixel overhang both ways, exactly one tile, exact multiples; radius 1..4 x {5, 8, 16} segments, the shipped
+    (3, 8, 10) among them.  What a halo error would move, counted on the CPU at radius 3 / 8 segments and printed (the conditions for every
+    radius and segment count are asserted in tests/test_stage1_edges_host.py): at 35 x 131, 111 outlier decisions hang on the halo beyond a
+    vertical tile edge, 457 on the one beyond a horizontal edge, 34 on the diagonal tile's alone, and 241 fill decisions on the closing's
+    halo (floors 8 / 8 / 4 / 4); 70 / 317 / 5 / 86 at 17 x 65, 61 / 273 / 8 / 97 at 32 x 128, none at 16 x 64 (one tile)."""
+    from worldforge_amd import warp
+    img, mask, depth = se.corner_views(H, W, 7 * H + W)
+    fh = fv = fd = fc = 0
+    for f in range(img.shape[0]):
+        ids = se.segment_ids(depth[f], mask[f], 8)
+        full, a, b, c = se.halo_flips(ids, 3, MIN_NEIGHBORS[3])
+        fh, fv, fd, fc = fh + a, fv + b, fd + c, fc + se.closing_flips(ids, full)
+    print(f"{H}x{W} r 3 / 8 segments: flips vertical {fh} horizontal {fv} diagonal-only {fd} closing {fc}")
+    if (H, W) != (16, 64):
+        assert fh >= 8 and fv >= 8 and fc >= 4 and fd >= (4 if (H, W) == (35, 131) else 1)
+    odepth = (2.0 + 0.05 * np.random.default_rng(3).standard_normal((H, W))).astype(np.float32)
+    dev = [torch.from_numpy(a).to(DEV) for a in (img, mask, depth)]
+    od = torch.from_numpy(odepth).to(DEV)
+    filled = 0
+    for r in (1, 2, 3, 4):
+        for nseg in (5, 8, 16):
+            p = dict(min_neighbors=MIN_NEIGHBORS[r], neighbor_radius=r, min_valid_neighbors=2, max_crack_size=6, depth_threshold=0.1)
+            got = warp.crack_fill_ex(*dev, min_neighbors=p["min_neighbors"], neighbor_radius=r, min_valid_neighbors=2, num_segments=nseg,
+                                     original_depth=od, has_depth_conf=True, depth_threshold=0.1, max_crack_size=6)
+            filled += _check_views(got, img, mask, depth, p, nseg, odepth)
+    assert filled > 12 * 7
+
+
+def test_crack_fill_on_one_wide_view_beyond_every_capped_grid():
+    """17 x 15430 = 262 310 pixels in 2 x 242 = 484 tiles: more than the 1024 x 256 threads of the linear grids (k_cf_segid, k_cf_merge,
+    k_cfx_merge), than the 120 x 256 of k_cfx_stats and than the 256 tiles k_cfx_order sums per step.  wf_crack_fill_ex with the shipped
+    parameters and wf_crack_fill at radius 1 / 5 segments against their restatements; 18 of the 30 629 fills lie beyond pixel 262 144."""
+    from oracle import crackfill as ocf
+    from worldforge_amd import warp
+    H, W = se.WIDE_SHAPE
+    tiles = ((H + 15) // 16) * ((W + 63) // 64)
+    assert H * W > 1024 * 256 and tiles > 256
+    img, mask, depth = se.wide_view()
+    dev = [torch.from_numpy(a).to(DEV) for a in (img, mask, depth)]
+    p = dict(warp.RUN_WARP_DEFAULTS)
+    got = warp.crack_fill_ex(*dev, min_neighbors=p["min_neighbors"], neighbor_radius=p["neighbor_radius"],
+                             min_valid_neighbors=p["min_valid_neighbors"], num_segments=8)
+    filled = _check_views(got, img, mask, depth, p, 8, None)
+    tail = ((got[1][0].cpu().numpy() > 0) & (mask[0] == 0)).ravel()[1024 * 256:].sum()
+    print("wide view: filled", filled, "beyond pixel 262144:", int(tail))
+    assert filled > 10000 and tail >= 4
+    # radius 1 / min_neighbors 3 keeps the far run of the last row: a segment whose only partial sums lie beyond k_cfx_order's first 256 tiles
+    p1 = dict(p, min_neighbors=3, neighbor_radius=1)
+    got = warp.crack_fill_ex(*dev, min_neighbors=3, neighbor_radius=1, min_valid_neighbors=p["min_valid_neighbors"], num_segments=8)
+    _check_views(got, img, mask, depth, p1, 8, None)
+    kept = np.nonzero(got[2][0].cpu().numpy() == 20.0)
+    assert len(kept[0]) >= 10 and (kept[0] == H - 1).all() and kept[1].min() >= 64 * (256 - (W + 63) // 64)
+    q = dict(ocf.RUN_WARP_PARAMS)
+    oi, om, od = (t.cpu().numpy() for t in warp.crack_fill(*dev, min_neighbors=q["min_neighbors"], min_valid_neighbors=q["min_valid_neighbors"],
+                                                           num_segments=5))
+    wi, wm, wd = ocf.warp_frame_fill(img[0], mask[0], depth[0], q, 5)
+    np.testing.assert_array_equal(om[0], wm)
+    assert np.array_equal(np.isnan(od[0]), np.isnan(wd))
+    np.testing.assert_allclose(od[0][~np.isnan(wd)], wd[~np.isnan(wd)], rtol=1e-6)
+    assert np.abs(oi[0].astype(np.int32) - wi.astype(np.int32)).max() <= 1
+    assert ((wm > 0) & (mask[0] == 0)).sum() > 10000 and ((wm == 0) & (mask[0] > 0)).sum() > 100
+
+
+def test_small_crack_fill_on_one_wide_view():
+    """wf_fill_small_cracks at 17 x 15430 (its grids are capped at 1024 x 256 threads too) against the oracle's fill_small_cracks: masks
+    exact, colours within one grey level; 128 082 holes, 42 617 closed by step 1, 1566 more by the depth-guided step, 48 beyond pixel
+    262 144."""
+    from oracle import crackfill as ocf
+    from worldforge_amd import warp
+    img, mask, odepth = se.sparse_view()
+    assert mask.size > 1024 * 256
+    want_i, want_m = ocf.fill_small_cracks_depth_guided(img.astype(np.float32) / 255.0, mask, odepth, True, 0.1, 6, 2)
+    step1 = ocf.fill_small_cracks(img.astype(np.float32) / 255.0, mask, 2)[1]
+    oi, om = warp.small_crack_fill(torch.from_numpy(img).to(DEV), torch.from_numpy(mask).to(DEV), torch.from_numpy(odepth).to(DEV), True, 0.1, 6, 2)
+    om = om.cpu().numpy()
+    print("small cracks, wide view: holes", int((mask == 0).sum()), "step 1", int(((step1 > 0) & (mask == 0)).sum()), "both steps",
+          int(((want_m > 0) & (mask == 0)).sum()), "beyond pixel 262144:", int(((want_m > 0) & (mask == 0)).ravel()[1024 * 256:].sum()))
+    assert int((want_m > step1).sum()) > 500 and ((want_m > 0) & (mask == 0)).ravel()[1024 * 256:].sum() >= 8
+    assert np.array_equal(om, want_m)
+    want_u8 = (want_i * 255).astype(np.uint8)
+    assert np.abs(oi.cpu().numpy().astype(np.int32) - want_u8.astype(np.int32)).max() <= 1
 
 
 # ---- the chain against the recorded reference -----------------------------------------------------------------------------------------------

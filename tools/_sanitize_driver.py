@@ -260,7 +260,7 @@ ok("wf_cl_to_ncthw", f32(npix * 32), f32(3 * npix), 3, 32, npix, 1.0, None)
 Hh, Ww, nv = 40, 56, 3
 geo = np.zeros(30, dtype=np.float64); cams = np.zeros(nv * 12, dtype=np.float64); KEEP += [geo, cams]
 ok("wf_warp_splat", f32(Hh * Ww * 3), f32(Hh * Ww, 2.0), geo.ctypes.data, cams.ctypes.data, buf(nv * Hh * Ww * 3), buf(nv * Hh * Ww), f32(nv * Hh * Ww),
-   buf(8 * nv * Hh * Ww), nv, Hh, Ww, None)
+   buf(12 * nv * Hh * Ww), nv, Hh, Ww, None)
 ok("wf_crack_fill", buf(nv * Hh * Ww * 3), buf(nv * Hh * Ww, 1), f32(nv * Hh * Ww, 2.0), buf(nv * Hh * Ww * 3), buf(nv * Hh * Ww), f32(nv * Hh * Ww), nv, Hh, Ww,
    4, 3, 5, buf(dll.wf_crack_fill_workspace_bytes(nv, Hh, Ww)), None)
 bad("wf_crack_fill", buf(64), buf(64), f32(16), buf(64), buf(64), f32(16), 1, 4, 4, 4, 3, 9, buf(4096), None)          # more segments than the kernel keeps

@@ -1,7 +1,8 @@
 // Stage-1 depth-guided forward warping (vggt/modules/utils_warp.py:863-945, warp_single_img): every source pixel with a valid depth is
 // un-projected, moved to each new camera, projected and rounded to the nearest target pixel; the NEAREST source (smallest camera-space z:
 // the reference sorts far-to-near and lets the last write win) owns the target pixel.  Integer / byte scatter work, HBM- and atomic-bound:
-// pass 1 scatters a sortable 64-bit image of z with atomicMin into a z-buffer, pass 2 lets the winner write colour, mask and depth.
+// pass 1 scatters a sortable 64-bit image of z with atomicMin into a z-buffer, pass 2 picks the owner among the sources that hold the
+// winning z (atomicMin of the source index: the lowest wins a tie), pass 3 writes colour, mask and depth of every target pixel.
 // All geometry in fp64, as the reference's numpy (float64 matrices, float32 depth).
 #include "common.h"
 
@@ -16,6 +17,9 @@ struct WarpGeom {      // doubles, row-major
 __device__ __forceinline__ unsigned long long zkey(double z) {  // order-preserving map double -> uint64
   unsigned long long u = (unsigned long long)__double_as_longlong(z);
   return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double zunkey(unsigned long long k) {
+  return __longlong_as_double((long long)((k & 0x8000000000000000ull) ? (k ^ 0x8000000000000000ull) : ~k));
 }
 
 // returns false when the source pixel does not land in the target image of camera `cam` (R|t rows in cams[12])
@@ -60,10 +64,10 @@ __global__ void k_warp_zpass(const float* __restrict__ depth, const double* __re
       atomicMin(&zbuf[(size_t)c * hw + (size_t)tv * W + tu], zkey(z));
   }
 }
-__global__ void k_warp_write(const float* __restrict__ image, const float* __restrict__ depth, const double* __restrict__ params,
-                             const double* __restrict__ cams, const unsigned long long* __restrict__ zbuf,
-                             unsigned char* __restrict__ out_img, unsigned char* __restrict__ out_mask, float* __restrict__ out_depth, int n,
-                             int H, int W) {
+// pass 2: among the sources whose key equals the z-buffer's (bit-equal z: a flat depth region under a pure translation), the one with the
+// lowest raster index owns the target -- a rule, where separate byte stores of every tied source would be a race
+__global__ void k_warp_owner(const float* __restrict__ depth, const double* __restrict__ params, const double* __restrict__ cams,
+                             const unsigned long long* __restrict__ zbuf, unsigned* __restrict__ owner, int n, int H, int W) {
   const WarpGeom& g = *reinterpret_cast<const WarpGeom*>(params);
   const size_t hw = (size_t)H * W, total = hw * n;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -74,10 +78,28 @@ __global__ void k_warp_write(const float* __restrict__ image, const float* __res
     if (!project(g, cams + 12 * c, (int)(p % W), (int)(p / W), depth[p], H, W, tu, tv, z)) continue;
     const size_t t = (size_t)c * hw + (size_t)tv * W + tu;
     if (zbuf[t] != zkey(z)) continue;  // a nearer source owns this target pixel
+    atomicMin(&owner[t], (unsigned)p);
+  }
+}
+// pass 3, one thread per TARGET: the owner's colour, mask and its z (the key read back: the same bits the owner computed) -- or an
+// empty pixel: image / mask = 0, depth = NaN (utils_warp.py:879-892)
+__global__ void k_warp_write(const float* __restrict__ image, const unsigned long long* __restrict__ zbuf, const unsigned* __restrict__ owner,
+                             unsigned char* __restrict__ out_img, unsigned char* __restrict__ out_mask, float* __restrict__ out_depth,
+                             size_t hw, size_t total) {
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+    const unsigned p = owner[t];
+    unsigned char rgb[3] = {0, 0, 0}, m = 0;
+    float d = __uint_as_float(0xffffffffu);
+    if (p != 0xffffffffu) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) out_img[t * 3 + k] = (unsigned char)(image[p * 3 + k] * 255.0f);  // (img * 255).astype(uint8), :931-932
-    out_mask[t] = 1;
-    out_depth[t] = (float)z;
+      for (int k = 0; k < 3; ++k) rgb[k] = (unsigned char)(image[(size_t)p * 3 + k] * 255.0f);  // (img * 255).astype(uint8), :931-932
+      m = 1;
+      d = (float)zunkey(zbuf[t]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out_img[t * 3 + k] = rgb[k];
+    out_mask[t] = m;
+    out_depth[t] = d;
   }
 }
 
@@ -89,14 +111,17 @@ extern "C" int wf_warp_splat(const float* image, const float* depth, const doubl
   WF_CHECK_ARG(n_cameras > 0 && H > 0 && W > 0, "wf_warp_splat: empty problem");
   hipStream_t s = (hipStream_t)stream;
   const size_t total = (size_t)n_cameras * H * W;
-  // z-buffer = +inf keys, images / masks = 0, depth = NaN (utils_warp.py:879-892)
-  if (hipMemsetAsync(zbuffer, 0xff, total * 8, s) != hipSuccess || hipMemsetAsync(out_images, 0, total * 3, s) != hipSuccess ||
-      hipMemsetAsync(out_masks, 0, total, s) != hipSuccess || hipMemsetAsync(out_depth, 0xff, total * 4, s) != hipSuccess)
-    return check_hip(hipGetLastError(), "wf_warp_splat");
+  WF_CHECK_ARG((size_t)H * W < 0xffffffffull, "wf_warp_splat: H=%d W=%d: a source index must fit 32 bits", H, W);
+  // z-buffer = +inf keys, owners = none; pass 3 writes every output element
+  unsigned long long* zbuf = (unsigned long long*)zbuffer;
+  unsigned* owner = (unsigned*)(zbuf + total);
+  if (hipMemsetAsync(zbuffer, 0xff, total * 12, s) != hipSuccess) return check_hip(hipGetLastError(), "wf_warp_splat");
   const int grid = grid_for(total, 256, 16384);
-  hipLaunchKernelGGL(k_warp_zpass, dim3(grid), dim3(256), 0, s, depth, geometry, cameras, (unsigned long long*)zbuffer, n_cameras, H, W);
-  hipLaunchKernelGGL(k_warp_write, dim3(grid), dim3(256), 0, s, image, depth, geometry, cameras, (const unsigned long long*)zbuffer,
-                     (unsigned char*)out_images, (unsigned char*)out_masks, out_depth, n_cameras, H, W);
+  hipLaunchKernelGGL(k_warp_zpass, dim3(grid), dim3(256), 0, s, depth, geometry, cameras, zbuf, n_cameras, H, W);
+  hipLaunchKernelGGL(k_warp_owner, dim3(grid), dim3(256), 0, s, depth, geometry, cameras, (const unsigned long long*)zbuf, owner, n_cameras, H,
+                     W);
+  hipLaunchKernelGGL(k_warp_write, dim3(grid), dim3(256), 0, s, image, (const unsigned long long*)zbuf, (const unsigned*)owner,
+                     (unsigned char*)out_images, (unsigned char*)out_masks, out_depth, (size_t)H * W, total);
   WF_LAUNCH_CHECK("wf_warp_splat");
   return WF_OK;
 }

@@ -38,7 +38,7 @@ def forward_splat(image: torch.Tensor, depth: torch.Tensor, intrinsic, extrinsic
     out_img = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
     out_mask = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
     out_depth = torch.empty((n, H, W), dtype=torch.float32, device=dev)
-    zbuf = torch.empty((n, H, W), dtype=torch.int64, device=dev)
+    zbuf = torch.empty((3 * n * H * W + 1) // 2, dtype=torch.int64, device=dev)  # 12 bytes per target: 64-bit depth key + 32-bit owner
     call("wf_warp_splat", img.data_ptr(), dep.data_ptr(), geom_d.data_ptr(), cams_d.data_ptr(), out_img.data_ptr(), out_mask.data_ptr(),
          out_depth.data_ptr(), zbuf.data_ptr(), n, H, W, ops.stream())
     return out_img, out_mask, out_depth
