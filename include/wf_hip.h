@@ -666,6 +666,32 @@ int wf_points_render(const float* points, const float* features, const void* dro
 size_t wf_depth_edge_mask_workspace_bytes(int H, int W);
 int wf_depth_edge_mask(const float* depth, int H, int W, double edge_threshold, int edge_dilation, float jump_threshold, int neighbor_radius,
                        void* out_drop, void* workspace, void* stream);
+/* The whole frame loop of run_warping (DepthCrafter/warp_depthcrafter.py:257-290) for T frames in one call: per frame
+ * depth_frame = 1.0f / (disparity + 0.1f) (:259), the point ((j - cx) * z) / fx, ((i - cy) * z) / fy, z (:262-266, never stored), for the
+ * frames t >= edge_filter_from the edge filter of wf_depth_edge_mask on depth_frame with that frame's own Sobel maximum (:269-281; the
+ * reference passes 1, a value >= T switches the filter off), one z-buffer per frame with wf_points_render's key and tie rule, the 5 x 5
+ * opening (morph != 0), image = owner's colour inside the mask, 0 outside (:283-287), and the 8-bit frame cv2.imwrite makes of the float32
+ * image (:292-294: convertTo(CV_8U) = the fp32 product x * 255.0f rounded to nearest, ties to even, then saturated; RESTATED and unpinned
+ * like the other OpenCV pieces).  Every square-window minimum / maximum runs as a row pass and a column pass; border rules as in the
+ * per-frame entry points (morphology ignores the outside, Sobel reflect-101, jump test scipy "reflect").  No floating-point atomics: the
+ * Sobel maxima are integer maxima on the bits of non-negative doubles.
+ * frames f32 [T][H][W][3] in [0, 1]; disparity f32 [T][H][W] (the content of depth.npz); cameras f32 [T][16] ON THE DEVICE, each as
+ * wf_points_render's camera; fx, fy, cx, cy = K.  out_images u8 [T][H][W][3], out_masks u8 [T][H][W] (0 / 1), out_images_f32 f32
+ * [T][H][W][3] or NULL.  Refused (WF_EINVAL): T, H or W <= 0; T > 65535; H or W < 2; H * W >= 2^31; radius outside (0, 0.05]; edge_dilation or
+ * neighbor_radius outside 0..15; edge_filter_from < 0.  workspace: wf_dc_warp_frames_workspace_bytes(T, H, W) bytes (11 per pixel), no
+ * initialisation needed. */
+size_t wf_dc_warp_frames_workspace_bytes(int T, int H, int W);
+int wf_dc_warp_frames(const float* frames, const float* disparity, const float* cameras, float fx, float fy, float cx, float cy,
+                      double edge_threshold, int edge_dilation, float jump_threshold, int neighbor_radius, int edge_filter_from, float radius,
+                      int morph, int T, int H, int W, void* out_images, void* out_masks, float* out_images_f32, void* workspace, void* stream);
+/* torchvision.transforms.functional.resize(frames, (H, W)) on a float tensor (warp_depthcrafter.py:203) =
+ * torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=antialias != 0), channels-last: in f32 [T][h][w][3] ->
+ * out f32 [T][H][W][3], columns first, then rows, each output index with its own weight row.  antialias: scale = in / out, support =
+ * max(scale, 1), centre = scale (i + 0.5), taps max(0, int(centre - support + 0.5)) .. min(in, int(centre + support + 0.5)), triangle
+ * weights at (j - centre + 0.5) / max(scale, 1), normalised by their sum.  Without: the two taps around scale (i + 0.5) - 0.5 (clamped at
+ * 0).  Equal sizes copy the input bits.  workspace: wf_resize_bilinear_aa_f32_workspace_bytes(T, h, w, H, W, antialias) bytes. */
+size_t wf_resize_bilinear_aa_f32_workspace_bytes(int T, int h, int w, int H, int W, int antialias);
+int wf_resize_bilinear_aa_f32(const float* in, float* out, int T, int h, int w, int H, int W, int antialias, void* workspace, void* stream);
 
 /* ---- measurement aid (bench.py `box_calib_tflops`) -------------------------------------------------------------------------------------
  * One launch of a fixed register-only stream of v_mfma_f32_32x32x16_bf16 (256 workgroups x 4 waves, one per SIMD, 16 accumulator tiles per

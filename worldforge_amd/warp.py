@@ -5,6 +5,10 @@ image + depth map -> n warped views with validity masks (the `warp_*` / `mask_*`
 camera paths (:64-383) are 4x4 host math (`camera_path`); the confidence filter (:774-808) is `depth_conf_filter` (np.percentile's
 threshold from an exact select on the device, the mean in fp64); `warp_single_img` joins them as the reference does, and
 `python -m worldforge_amd.run_warp` is its command line.
+
+Dynamic scenes (DepthCrafter/warp_depthcrafter.py run_warping :140-301: every frame of a clip warped to its own camera) are at the end of
+the file: the camera sequences, `warp_depthcrafter_frames` and the batched `dc_warp_frames`; `python -m worldforge_amd.warp_depthcrafter`
+is their command line.
 """
 from __future__ import annotations
 
@@ -402,3 +406,218 @@ def render_depthcrafter_frame(rgb: torch.Tensor, depth_frame: torch.Tensor, cam,
     pts = torch.stack(((jj - float(Kf[0, 2])) * d / float(Kf[0, 0]), (ii - float(Kf[1, 2])) * d / float(Kf[1, 1]), d), dim=-1).reshape(-1, 3)
     drop = depth_edge_mask(d, **edge_kw).reshape(-1) if edge_filter else None
     return points_render(pts, rgb.reshape(-1, 3), cam, K, (H, W), morph=True, drop=drop)
+
+
+# ---- dynamic scenes, the whole route: DepthCrafter/warp_depthcrafter.py run_warping (:140-301) ---------------------------------------------
+# Camera sequences (DepthCrafter/utils.py:240-492): float64 host math.  A "camera" here is what the reference builds -- a 4x4 whose rotation
+# block is look_at's matrix and whose last column is the camera POSITION -- and hands to the renderer as the extrinsic, unchanged.
+def dc_look_at(camera_pos, target, up) -> np.ndarray:
+    """utils.py:240-250: the columns are right, up, forward of a camera at camera_pos aimed at target."""
+    forward = np.asarray(target, dtype=np.float64) - np.asarray(camera_pos, dtype=np.float64)
+    forward = forward / np.linalg.norm(forward)
+    right = np.cross(up, forward)
+    right = right / np.linalg.norm(right)
+    return np.vstack([right, np.cross(forward, right), forward]).T
+
+
+def _dc_orbit_camera(extrinsic, degree: float, depth: float, axis: int) -> np.ndarray:
+    """get_look_up_camera (axis 1, :253-278) / get_look_right_camera (axis 0, with the angle negated, :281-306).  The target is taken from
+    the position BEFORE it moves: the reference moves `t` in place after it has formed look_at_point."""
+    E = np.asarray(extrinsic, dtype=np.float64)
+    pos, R = E[:3, 3].copy(), E[:3, :3].copy()
+    target = pos + R @ np.array([0, 0, depth], dtype=np.float64)
+    rad = np.deg2rad(degree if axis == 1 else -degree)
+    pos[axis] = pos[axis] + np.sin(rad) * depth
+    pos[2] = pos[2] + (1 - np.cos(rad)) * depth
+    cam = np.eye(4)
+    cam[:3, :3] = dc_look_at(pos, target, np.array([0, 1, 0]))
+    cam[:3, 3] = pos
+    return cam
+
+
+def _dc_stable_degrees(max_degree: float, frame_num: int, stable_frame: int):
+    """:412-447: the angle reaches max_degree at frame stable_frame - 1 and stays there."""
+    sf = min(stable_frame, frame_num)
+    return [(i / (sf - 1)) * max_degree if (i < sf and sf > 1) else max_degree for i in range(frame_num)]
+
+
+def dc_look_up_camera_seq(extrinsics, max_degree, frame_num, look_at_depth):
+    """get_look_up_camera_seq (:309-319)."""
+    return [_dc_orbit_camera(extrinsics, d, float(look_at_depth), 1) for d in np.linspace(0, max_degree, frame_num)]
+
+
+def dc_look_right_camera_seq(extrinsics, max_degree, frame_num, look_at_depth):
+    """get_look_right_camera_seq (:322-332)."""
+    return [_dc_orbit_camera(extrinsics, d, float(look_at_depth), 0) for d in np.linspace(0, max_degree, frame_num)]
+
+
+def dc_stable_look_up_camera_seq(extrinsics, max_degree, frame_num, look_at_depth, stable_frame=17):
+    """get_stable_look_up_camera_seq (:412-428)."""
+    return [_dc_orbit_camera(extrinsics, d, float(look_at_depth), 1) for d in _dc_stable_degrees(max_degree, frame_num, stable_frame)]
+
+
+def dc_stable_look_right_camera_seq(extrinsics, max_degree, frame_num, look_at_depth, stable_frame=17):
+    """get_stable_look_right_camera_seq (:431-447)."""
+    return [_dc_orbit_camera(extrinsics, d, float(look_at_depth), 0) for d in _dc_stable_degrees(max_degree, frame_num, stable_frame)]
+
+
+def _dc_zoom(cams, zoom_mode, rate, look_at_depth, progress):
+    if zoom_mode == "none":
+        return cams
+    if not (0.0 < rate <= 1.0):
+        raise ValueError("rate must be between 0.0 and 1.0")
+    out = []
+    for i, cam in enumerate(cams):
+        pos, R = cam[:3, 3].copy(), cam[:3, :3].copy()
+        target = pos + R @ np.array([0, 0, float(look_at_depth)], dtype=np.float64)
+        away = pos - target
+        p = progress(i)
+        factor = 1.0 - p * (1.0 - rate) if zoom_mode == "zoom_out" else (1.0 + p * (1.0 / rate - 1.0) if zoom_mode == "zoom_in" else 1.0)
+        new_pos = target + away * factor
+        new = np.eye(4)
+        new[:3, :3] = dc_look_at(new_pos, target, np.array([0, 1, 0]))
+        new[:3, 3] = new_pos
+        out.append(new)
+    return out
+
+
+def dc_apply_zoom_to_camera_seq(cams, zoom_mode, rate, look_at_depth):
+    """apply_zoom_to_camera_seq (:371-409): every camera moves along its line to the point look_at_depth in front of it, to `rate` times
+    the distance (zoom_out) or 1 / rate times (zoom_in) at the last frame."""
+    n = len(cams)
+    return _dc_zoom(cams, zoom_mode, rate, look_at_depth, lambda i: i / (n - 1) if n > 1 else 0.0)
+
+
+def dc_apply_stable_zoom_to_camera_seq(cams, zoom_mode, rate, look_at_depth, stable_frame=17):
+    """apply_stable_zoom_to_camera_seq (:450-492): the same, complete at frame stable_frame - 1."""
+    sf = min(stable_frame, len(cams))
+    return _dc_zoom(cams, zoom_mode, rate, look_at_depth, lambda i: i / (sf - 1) if (i < sf and sf > 1) else 1.0)
+
+
+def depthcrafter_cameras(direction, degree, frame_num, look_at_depth_value, zoom="none", rate=0.8, stable=False, stable_frame=17):
+    """The dispatch of run_warping (:211-247) from the identity extrinsic: `down` and `left` negate the angle; zoom, if any, is laid over the
+    sequence; the rate check is main()'s (:374-375).  -> frame_num 4x4 float64 arrays."""
+    if zoom not in ("zoom_in", "zoom_out", "none"):
+        raise ValueError(f"Unsupported zoom: {zoom}")
+    if zoom != "none" and not (0.0 < rate <= 1.0):
+        raise ValueError(f"Rate must be between 0.0 and 1.0, got {rate}")
+    if direction not in ("up", "down", "left", "right"):
+        raise ValueError(f"Unsupported direction: {direction}")
+    E = np.eye(4)
+    deg = degree if direction in ("up", "right") else -degree
+    if stable:
+        seq = dc_stable_look_up_camera_seq if direction in ("up", "down") else dc_stable_look_right_camera_seq
+        cams = seq(E, deg, frame_num, look_at_depth_value, stable_frame)
+        if zoom != "none":
+            cams = dc_apply_stable_zoom_to_camera_seq(cams, zoom, rate, look_at_depth_value, stable_frame)
+    else:
+        seq = dc_look_up_camera_seq if direction in ("up", "down") else dc_look_right_camera_seq
+        cams = seq(E, deg, frame_num, look_at_depth_value)
+        if zoom != "none":
+            cams = dc_apply_zoom_to_camera_seq(cams, zoom, rate, look_at_depth_value)
+    return cams
+
+
+def median_index(n: int) -> int:
+    """The k of wf_select_pair_f32 whose pair np.median(a) of n values needs: sorted[(n - 1) // 2] and its successor."""
+    return (int(n) - 1) // 2
+
+
+def median_from_pair(lo, hi, n: int) -> np.float32:
+    """np.median of n float32 values from (sorted[k], sorted[k + 1]), k = median_index(n): the lower value itself for odd n, for even n the
+    float32 mean as numpy forms it (the float32 sum, divided by 2)."""
+    lo, hi = np.float32(lo), np.float32(hi)
+    return lo if n % 2 else np.float32(np.float32(lo + hi) / np.float32(2))
+
+
+def median_f32(x: torch.Tensor) -> np.float32:
+    """np.median(x) of an fp32 device tensor, bit for bit; a NaN in x is a ValueError (numpy would return NaN)."""
+    n = x.numel()
+    lo, hi, nans = select_pair(x, median_index(n))
+    if nans:
+        raise ValueError(f"median_f32: {nans} NaN value(s) in the input (numpy's median would be NaN)")
+    return median_from_pair(lo, hi, n)
+
+
+def resize_bilinear(frames: torch.Tensor, size_hw, antialias: bool = True) -> torch.Tensor:
+    """torchvision.transforms.functional.resize(frames, (H, W)) of float frames, channels-last: f32 [T, h, w, 3] (device) -> [T, H, W, 3]
+    (wf_resize_bilinear_aa_f32).  antialias=True is torchvision's default on tensors since 0.17; older releases default to False (plain
+    bilinear, which differs when the frames shrink).  Which release the reference's users run is unpinned."""
+    from ._ffi import lib
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"frames must be [T, h, w, 3], got {tuple(frames.shape)}")
+    frames = frames.to(torch.float32).contiguous()
+    T, h, w, _ = frames.shape
+    H, W = int(size_hw[0]), int(size_hw[1])
+    aa = 1 if antialias else 0
+    ws = torch.empty(int(lib().wf_resize_bilinear_aa_f32_workspace_bytes(T, h, w, H, W, aa)), dtype=torch.uint8, device=frames.device)
+    out = torch.empty((T, H, W, 3), dtype=torch.float32, device=frames.device)
+    call("wf_resize_bilinear_aa_f32", frames.data_ptr(), out.data_ptr(), T, h, w, H, W, aa, ws.data_ptr(), ops.stream())
+    return out
+
+
+DC_WORKSPACE_BUDGET = 2 << 30  # bytes of wf_dc_warp_frames workspace above which warp_depthcrafter_frames splits the frames into chunks
+
+
+def dc_warp_frames(rgb: torch.Tensor, disparity: torch.Tensor, cams, K, edge_filter_from: int = 1, edge_threshold: float = 0.1,
+                   edge_dilation: int = 3, depth_jump_threshold: float = 0.3, neighbor_check_radius: int = 2, radius: float = 0.005,
+                   morph: bool = True, return_float: bool = False, workspace_budget: int = None, K_points=None):
+    """wf_dc_warp_frames: rgb f32 [T, H, W, 3] in [0, 1], disparity f32 [T, H, W] (device), cams T 4x4 (host), K 3x3 -> (images u8
+    [T, H, W, 3], masks u8 [T, H, W][, float images f32 [T, H, W, 3]]).  Frames t >= edge_filter_from get the edge filter.  One call, unless
+    its workspace (11 bytes per pixel) exceeds workspace_budget (default DC_WORKSPACE_BUDGET): then one call per chunk of frames.
+    K_points: the intrinsics the pixels are un-projected with, where they differ from the camera's K (the reference uses one K for both)."""
+    from ._ffi import lib
+    rgb, disparity = rgb.to(torch.float32).contiguous(), disparity.to(torch.float32).contiguous()
+    T, H, W = disparity.shape
+    if tuple(rgb.shape) != (T, H, W, 3) or len(cams) != T:
+        raise ValueError(f"rgb {tuple(rgb.shape)}, disparity {tuple(disparity.shape)} and {len(cams)} cameras do not match")
+    dev = disparity.device
+    Kf = np.asarray(K, dtype=np.float32)
+    cam16 = torch.from_numpy(np.stack([pytorch3d_camera(c, Kf, (H, W)) for c in cams])).to(dev)
+    Kp = Kf if K_points is None else np.asarray(K_points, dtype=np.float32)
+    images = torch.empty((T, H, W, 3), dtype=torch.uint8, device=dev)
+    masks = torch.empty((T, H, W), dtype=torch.uint8, device=dev)
+    fimg = torch.empty((T, H, W, 3), dtype=torch.float32, device=dev) if return_float else None
+    budget = DC_WORKSPACE_BUDGET if workspace_budget is None else int(workspace_budget)
+    chunk = min(T, max(1, budget // max(1, int(lib().wf_dc_warp_frames_workspace_bytes(1, H, W)))))
+    ws = torch.empty(int(lib().wf_dc_warp_frames_workspace_bytes(chunk, H, W)), dtype=torch.uint8, device=dev)
+    for t0 in range(0, T, chunk):
+        n = min(chunk, T - t0)
+        call("wf_dc_warp_frames", rgb[t0:].data_ptr(), disparity[t0:].data_ptr(), cam16[t0:].data_ptr(), float(Kp[0, 0]), float(Kp[1, 1]),
+             float(Kp[0, 2]), float(Kp[1, 2]), float(edge_threshold), int(edge_dilation), float(depth_jump_threshold),
+             int(neighbor_check_radius), max(0, int(edge_filter_from) - t0), float(radius), 1 if morph else 0, n, H, W,
+             images[t0:].data_ptr(), masks[t0:].data_ptr(), fimg[t0:].data_ptr() if return_float else None, ws.data_ptr(), ops.stream())
+    return (images, masks, fimg) if return_float else (images, masks)
+
+
+def warp_depthcrafter_frames(frames, disparity, direction="left", degree=15.0, look_at_depth=1.0, zoom="none", rate=0.8, stable=False,
+                             stable_frame=17, enable_edge_filter=False, edge_threshold=0.1, edge_dilation=3, depth_jump_threshold=0.3,
+                             neighbor_check_radius=2, antialias=True, return_float=False, device="cuda:0"):
+    """run_warping (warp_depthcrafter.py:201-290) on the device: frames [T, h, w, 3], u8 or float holding 0..255 (what an image reader
+    returns); disparity [T, H, W] (the `depth` of depth.npz).  frames / 255 -> resize to H x W (resize_bilinear; `antialias` as there) ->
+    K = [[525, 0, W / 2], [0, 525, H / 2]] in float32 -> look-at depth = np.median(1 / (disparity[0] + 0.1)) * look_at_depth in float32 ->
+    depthcrafter_cameras -> dc_warp_frames (frame 0 never gets the edge filter).  -> (images u8 [T, H, W, 3], masks u8 [T, H, W], cams
+    [, float images]) with images and masks on the device.
+    ValueError: shapes other than [T, h, w, 3] / [T, H, W]; a frame count that differs from the depth's; a NaN in frame 0's depth."""
+    dev = torch.device(device)
+    fr, disp = torch.as_tensor(frames), torch.as_tensor(disparity)
+    if fr.dim() != 4 or fr.shape[3] != 3:
+        raise ValueError(f"frames must be [T, h, w, 3], got {tuple(fr.shape)}")
+    if disp.dim() != 3:
+        raise ValueError(f"disparity must be [T, H, W], got {tuple(disp.shape)}")
+    if fr.shape[0] != disp.shape[0]:
+        raise ValueError(f"{fr.shape[0]} frames but {disp.shape[0]} depth maps")
+    T, H, W = disp.shape
+    disp = disp.to(dev).to(torch.float32).contiguous()
+    rgb = resize_bilinear(fr.to(dev) / 255.0, (H, W), antialias=antialias)
+    K = np.array([[525.0, 0, 0.5 * W], [0, 525.0, 0.5 * H], [0, 0, 1]], dtype=np.float32)
+    try:
+        med = median_f32(1.0 / (disp[0] + 0.1))
+    except ValueError as e:
+        raise ValueError(f"warp_depthcrafter_frames: NaN in the depth of frame 0 ({e})") from None
+    look = float(np.float32(med * np.float32(look_at_depth)))  # np.float32 * float stays float32, as in the reference
+    cams = depthcrafter_cameras(direction, degree, T, look, zoom, rate, stable, stable_frame)
+    out = dc_warp_frames(rgb, disp, cams, K, edge_filter_from=1 if enable_edge_filter else T, edge_threshold=edge_threshold,
+                         edge_dilation=edge_dilation, depth_jump_threshold=depth_jump_threshold, neighbor_check_radius=neighbor_check_radius,
+                         return_float=return_float)
+    return (out[0], out[1], cams) + tuple(out[2:])
