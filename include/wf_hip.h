@@ -652,29 +652,32 @@ int wf_fill_small_cracks(const void* img, const void* mask, const float* origina
                          int H, int W, float depth_threshold, int max_crack_size, int min_valid_neighbors, void* workspace, void* stream);
 
 /* ---- stage-1 of the dynamic-scene path: DepthCrafter point-cloud renderer (DepthCrafter/utils.py, warp_depthcrafter.py:255-288) ------- */
+/* The three entry points below run one set of kernels: wf_points_render and wf_depth_edge_mask are the two halves of wf_dc_warp_frames at
+ * T = 1, fed from a stored point array / depth plane instead of the disparity.  Every square window runs as a row and a column pass. */
 /* project_points_to_image_pytorch (utils.py:103-171): pytorch3d PointsRasterizer(radius, points_per_pixel = 10) -> idx[..., 0] = the
  * covering point of smallest view depth per pixel -> image = features[idx], mask = idx != -1 -> 5 x 5 opening of the mask (morph) ->
  * image zeroed outside it.  points f32 [n][3] (world), features f32 [n][F], drop (NULL or u8 [n]: 1 = point removed by the edge filter);
  * camera = 16 floats in pytorch3d's convention {R' (9, row-major, view = p R' + T'), T' (3), focal' (2), principal' (2)}, i.e. the result
  * of _cameras_from_opencv_projection for the reference's (extrinsic, K, image size) -- computed by the host (worldforge_amd/warp.py).
- * out_image f32 [H][W][F], out_mask u8 [H][W].  pytorch3d / OpenCV are absent from the reference tree: parity with them is unpinned. */
+ * out_image f32 [H][W][F], out_mask u8 [H][W].  pytorch3d / OpenCV are absent from the reference tree: parity with them is unpinned.
+ * The z-buffer key is view depth bits << 32 | point index: the nearest point wins, an exact tie goes to the smaller index. */
 size_t wf_points_render_workspace_bytes(int H, int W);
 int wf_points_render(const float* points, const float* features, const void* drop, int n, int F, const float* camera, int H, int W,
                      float radius, int morph, float* out_image, void* out_mask, void* workspace, void* stream);
 /* filter_edge_points (utils.py:523-567): out_drop u8 [H][W] = dilate_{2 d + 1}(Sobel magnitude / its maximum > edge_threshold) |
- * (max - min of the depth over the (2 r + 1)^2 window > jump_threshold); depth f32 [H][W].  d = edge_dilation, r = neighbor_radius. */
+ * (max - min of the depth over the (2 r + 1)^2 window > jump_threshold); depth f32 [H][W].  d = edge_dilation, r = neighbor_radius.
+ * Borders: the dilation ignores the outside, Sobel reflect-101, jump test scipy "reflect". */
 size_t wf_depth_edge_mask_workspace_bytes(int H, int W);
 int wf_depth_edge_mask(const float* depth, int H, int W, double edge_threshold, int edge_dilation, float jump_threshold, int neighbor_radius,
                        void* out_drop, void* workspace, void* stream);
 /* The whole frame loop of run_warping (DepthCrafter/warp_depthcrafter.py:257-290) for T frames in one call: per frame
  * depth_frame = 1.0f / (disparity + 0.1f) (:259), the point ((j - cx) * z) / fx, ((i - cy) * z) / fy, z (:262-266, never stored), for the
  * frames t >= edge_filter_from the edge filter of wf_depth_edge_mask on depth_frame with that frame's own Sobel maximum (:269-281; the
- * reference passes 1, a value >= T switches the filter off), one z-buffer per frame with wf_points_render's key and tie rule, the 5 x 5
- * opening (morph != 0), image = owner's colour inside the mask, 0 outside (:283-287), and the 8-bit frame cv2.imwrite makes of the float32
+ * reference passes 1, a value >= T switches the filter off), one z-buffer per frame with wf_points_render's key and tie rule (the point
+ * index being the pixel's raster index in its frame), the 5 x 5 opening (morph != 0), image = owner's colour inside the mask, 0 outside (:283-287), and the 8-bit frame cv2.imwrite makes of the float32
  * image (:292-294: convertTo(CV_8U) = the fp32 product x * 255.0f rounded to nearest, ties to even, then saturated; RESTATED and unpinned
- * like the other OpenCV pieces).  Every square-window minimum / maximum runs as a row pass and a column pass; border rules as in the
- * per-frame entry points (morphology ignores the outside, Sobel reflect-101, jump test scipy "reflect").  No floating-point atomics: the
- * Sobel maxima are integer maxima on the bits of non-negative doubles.
+ * like the other OpenCV pieces).  The per-frame entry points are this call at T = 1.  No floating-point atomics: the Sobel maxima are
+ * integer maxima on the bits of non-negative doubles.
  * frames f32 [T][H][W][3] in [0, 1]; disparity f32 [T][H][W] (the content of depth.npz); cameras f32 [T][16] ON THE DEVICE, each as
  * wf_points_render's camera; fx, fy, cx, cy = K.  out_images u8 [T][H][W][3], out_masks u8 [T][H][W] (0 / 1), out_images_f32 f32
  * [T][H][W][3] or NULL.  Refused (WF_EINVAL): T, H or W <= 0; T > 65535; H or W < 2; H * W >= 2^31; radius outside (0, 0.05]; edge_dilation or

@@ -1,5 +1,6 @@
 """GPU: the dynamic-scene stage 1 -- wf_dc_warp_frames (the whole frame loop of DepthCrafter/warp_depthcrafter.py:257-290 in one call) against
-the per-frame entry points and oracle/pointrender.py, wf_resize_bilinear_aa_f32 against torch's CPU kernel, the whole route against the
+the per-frame entry points (the same kernels at T = 1), the bits all three returned before they shared kernels (g30_pointrender_parent.json)
+and oracle/pointrender.py, wf_resize_bilinear_aa_f32 against torch's CPU kernel, the whole route against the
 reference's recorded frames (G29, tools/make_dynamic_warp_golden.py) and the command line's hand-over to the sampler's frame reader.
 
 The renderer's radius is fixed (0.005 NDC units) and the reference un-projects pixel (i, j) to a pixel CORNER, so below a short side of
@@ -13,6 +14,7 @@ import torch
 
 from oracle import pointrender as opr
 from tests import dynwarp_cases as dc
+from tests import pointrender_cases as pc
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -42,19 +44,7 @@ def _moved(tx, th):
     return cam
 
 
-def _scene(T, H, W, seed, steps=(0.0, 0.02, 0.45)):
-    """rgb f32 [T, H, W, 3], disparity f32 [T, H, W]: frame t carries a box whose disparity step is steps[t] -- frames 1 and 2 differ in
-    their Sobel maximum by far more than 10 x -- over a gentle ripple, with features on every border."""
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:H, 0:W]
-    disp = np.empty((T, H, W), dtype=F32)
-    for t in range(T):
-        d = 0.3 + 0.004 * np.sin(xx / 9.0) + 0.004 * np.cos(yy / 11.0) + 0.0001 * rng.random((H, W))
-        d[H // 4:H // 4 + max(6, H // 3), W // 4:W // 4 + max(6, W // 3)] += steps[t % len(steps)]
-        d[:2, : W // 2] += steps[t % len(steps)]
-        d[H // 2:, W - 2:] += steps[t % len(steps)]
-        disp[t] = d
-    return rng.random((T, H, W, 3)).astype(F32), disp
+_scene = pc.scene
 
 
 def _per_frame(rgb, disp, cams, K, from_, Kp=None):
@@ -118,6 +108,53 @@ def test_batched_equals_per_frame(H, W, centred):
         assert cover[0] == 1.0 and 0.1 < cover[1] < 1.0 and 0.1 < cover[2] < 1.0, cover
     elif min(H, W) >= 283:
         assert (cover > 0.5).all() and (cover[1:] < 1.0).all(), cover
+
+
+@pytest.fixture(scope="module")
+def recorder():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("record_pointrender_digests", os.path.join(os.path.dirname(GOLD), os.pardir, "tools",
+                                                                                             "record_pointrender_digests.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("kind", ["points", "edge", "batch"])
+def test_entry_points_repeat_the_parent(kind, recorder):
+    """Every output bit of wf_points_render, wf_depth_edge_mask and wf_dc_warp_frames on tests/pointrender_cases.py equals what the commit
+    named in g30_pointrender_parent.json returned (sha256 of the bytes, recorded by tools/record_pointrender_digests.py from that commit's
+    build: its per-frame entry points still had kernels of their own).  So that the recorded bits are not merely repeated but right: at
+    radius 0.05 with dropped points the masks equal oracle.pointrender's on the live points and the images equal it on the pixels whose
+    nearest point has a live exact copy (the smaller index wins); the default edge filter equals the oracle's exactly."""
+    import json
+    from worldforge_amd import warp
+    with open(os.path.join(GOLD, "g30_pointrender_parent.json")) as f:
+        want = {k: v for k, v in json.load(f)["digests"].items() if k.startswith({"points": "pts_", "edge": "edge_", "batch": "batch_"}[kind])}
+    got = recorder.compute(DEV, kinds=(kind,))
+    assert set(got) == set(want) and len(want) >= {"points": 25, "edge": 60, "batch": 5}[kind]
+    moved = sorted(k for k in want if got[k] != want[k])
+    assert not moved, moved
+    if kind == "points":
+        from tests.test_pointrender_cases_host import owners, tie_pixels
+        for H, W in pc.POINT_SHAPES:
+            c = pc.points(H, W)
+            live = c["drop"] == 0
+            ties, _ = tie_pixels(c, owners(c, live), live)
+            assert ties.sum() >= 100
+            for morph in (True, False):
+                img, mask = recorder.render_points(c, dict(radius=0.05, morph=morph, use_drop=True), DEV)
+                with np.errstate(all="ignore"):
+                    wimg, wmask = opr.project_points_to_image(c["pts"][live], c["feats"][live], c["cam"], c["K"], (H, W), morph=morph, radius=0.05)
+                np.testing.assert_array_equal(mask, wmask[..., 0])
+                np.testing.assert_array_equal(img[ties], wimg[ties])
+                assert morph or mask[ties].all()
+    if kind == "edge":
+        for H, W in ((40, 56), (57, 33)):
+            depth = pc.edge_depths(H, W)
+            for t in range(3):
+                got_drop = warp.depth_edge_mask(torch.from_numpy(depth[t]).to(DEV)).cpu().numpy()
+                np.testing.assert_array_equal(got_drop.astype(bool), opr.edge_filter_mask(depth[t]))
 
 
 def _border_counts(diff):

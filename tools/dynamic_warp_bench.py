@@ -3,8 +3,8 @@ median of 9 after a warm-up, both arms in one process on one box.  Writes a mark
 
     python tools/dynamic_warp_bench.py [--out profiles/stage1_dynamic_warp.md] [--frames 49]
 
-Rows: the batched call (wf_dc_warp_frames, one call for all frames), the per-frame loop of the functions it replaces
-(warp.render_depthcrafter_frame per frame, the depth 1 / (d + 0.1) included as the loop computes it), the resize
+Rows: the batched call (wf_dc_warp_frames, one call for all frames), the loop of per-frame calls (warp.render_depthcrafter_frame per
+frame: the same kernels at T = 1 on a stored depth plane and point array, the depth 1 / (d + 0.1) included as the loop computes it), the resize
 (wf_resize_bilinear_aa_f32, antialias on) and the median of frame 0 (wf_select_pair_f32 + the 12-byte read).  Below them the resize's
 measured error against torch's CPU kernel on the test sizes (the bars of tests/dynwarp_cases.py are twice these).  No CPU fallback:
 without a GPU the tool fails."""

@@ -346,6 +346,7 @@ def small_crack_fill(image: torch.Tensor, mask: torch.Tensor, original_depth: to
 
 
 # ---- dynamic scenes: the DepthCrafter warper's per-frame point-cloud render (DepthCrafter/warp_depthcrafter.py:255-288) ------------------
+# (depth_edge_mask and points_render run the kernels of dc_warp_frames, further down, on one frame's stored depth plane / point array)
 def pytorch3d_camera(extrinsic, K, size_hw) -> np.ndarray:
     """The 16 floats wf_points_render takes: pytorch3d's view of the reference's (extrinsic, K, image size), i.e. what
     pytorch3d.utils.camera_conversions._cameras_from_opencv_projection builds at DepthCrafter/utils.py:119-124 -- R' = R^T with its first two
