@@ -695,6 +695,21 @@ int wf_dc_warp_frames(const float* frames, const float* disparity, const float* 
  * 0).  Equal sizes copy the input bits.  workspace: wf_resize_bilinear_aa_f32_workspace_bytes(T, h, w, H, W, antialias) bytes. */
 size_t wf_resize_bilinear_aa_f32_workspace_bytes(int T, int h, int w, int H, int W, int antialias);
 int wf_resize_bilinear_aa_f32(const float* in, float* out, int T, int h, int w, int H, int W, int antialias, void* workspace, void* stream);
+/* PIL.Image.resize on 8-bit images (Pillow's fixed-point resample, modes L and RGB), channels-last: in u8 [T][h][w][C] -> out u8
+ * [T][H][W][C], C = 1 or 3.  The caller supplies Pillow's tables per axis (worldforge_amd/resample.py: pil_resample_tables), ON THE DEVICE:
+ * bounds i32 [out][2] = (first tap, tap count), coefs i32 [out][k] = the normalised filter weights rounded to 22 fractional bits, zero
+ * behind the count.  One output sample is clamp(((1 << 21) + sum_j px[first + j] coefs[j]) >> 22, 0, 255) in int32 (arithmetic shift).
+ * Columns first into a u8 [T][h][W][C] intermediate in the workspace, then rows; w == W skips the column pass and h == H the row pass (the
+ * skipped pass's tables may be NULL), both equal copy the input.  No floating point, no atomics; the bytes do not depend on the grid.
+ * The tables are trusted: every first + count must lie inside its axis (the Python wrapper builds them itself).  Refused (WF_EINVAL):
+ * a size <= 0, C not 1 or 3, a null pointer, a pass without its tables or with k <= 0.  workspace: wf_resample_u8_workspace_bytes(...) bytes
+ * (NULL allowed when at most one pass runs). */
+size_t wf_resample_u8_workspace_bytes(int T, int h, int w, int H, int W, int C);
+int wf_resample_u8(const uint8_t* in, uint8_t* out, int T, int h, int w, int H, int W, int C, const int32_t* xbounds, const int32_t* xcoefs,
+                   int xk, const int32_t* ybounds, const int32_t* ycoefs, int yk, void* workspace, void* stream);
+/* 8-bit channels-last frames through a 256-entry table into planar floats: in u8 [T][h][w][C], lut f32 [256] (device) -> out f32
+ * [C][T][h][w], out = lut[in].  The table carries the host's own u8 -> f32 expression, so no division runs on the device. */
+int wf_u8_lut_planar_f32(const uint8_t* in, const float* lut, float* out, int T, int h, int w, int C, void* stream);
 
 /* ---- measurement aid (bench.py `box_calib_tflops`) -------------------------------------------------------------------------------------
  * One launch of a fixed register-only stream of v_mfma_f32_32x32x16_bf16 (256 workgroups x 4 waves, one per SIMD, 16 accumulator tiles per

@@ -110,6 +110,53 @@ def prepare_inputs(directory: str, model: str = "480p", num_frames: int = None, 
     return image, video_ref, mask, h, w
 
 
+def prepare_inputs_device(images_u8, masks_u8, model: str = "480p", num_frames: int = None, soften: bool = True,
+                          transition_distance: int = 15, decay_type: str = "sine", device=None, max_area: int = None, image=None, size=None):
+    """prepare_inputs for stage-1 tensors that are still on the device: images_u8 u8 [F, H, W, 3] and masks_u8 u8 [F, H, W] (0 / 1) as
+    warp.warp_single_img / warp.warp_depthcrafter_frames return them, in place of the directory their PNG files would be read from.
+    Same remaining arguments, same five values, and the tensors are bit-identical to prepare_inputs(directory, device=...) on the files
+    the stage-1 writers make of these tensors: PNG is lossless, the masks are scaled to 0 / 255 as the writers do, `PIL.Image.resize` is
+    ops.resample_u8 (Pillow's fixed-point bicubic on the device), the two u8 -> f32 conversions are 256-entry tables holding
+    prepare_inputs' own expressions (resample.u8_to_f32_tables), then ops.soften_mask.  Only the input image goes to the host: without
+    `image` it is images_u8[0], and the size rule and its `resize((w, h))` run on it there as in prepare_inputs.
+    Stated deviation: the frames keep the order stage 1 returned them in; the file route sorts the file names, which is the same
+    order for fewer than 100 frames and label angles below 100 degrees."""
+    from PIL import Image
+
+    from . import ops, resample
+    dev = torch.device(device) if device is not None else images_u8.device
+    if dev.type != "cuda":
+        raise RuntimeError("prepare_inputs_device needs a GPU device: there is no CPU fallback (use prepare_inputs on a directory)")
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise TypeError(f"images_u8: uint8 [F, H, W, 3], got {images_u8.dtype} {tuple(images_u8.shape)}")
+    if masks_u8.dtype != torch.uint8 or tuple(masks_u8.shape) != tuple(images_u8.shape[:3]):
+        raise TypeError(f"masks_u8: uint8 {tuple(images_u8.shape[:3])}, got {masks_u8.dtype} {tuple(masks_u8.shape)}")
+    images_u8, masks_u8 = images_u8.to(dev), masks_u8.to(dev)
+    if masks_u8.numel() and int(masks_u8.max()) > 1:    # 0 / 255 masks would wrap to 0 / 1 in the uint8 product below
+        raise ValueError(f"masks_u8 holds 0 / 1 as stage 1 returns it, got a maximum of {int(masks_u8.max())}")
+    masks_u8 = masks_u8 * 255
+    if image is not None:
+        if isinstance(image, (str, os.PathLike)):
+            image = Image.open(image).convert("RGB")
+        first = image
+    else:
+        if images_u8.shape[0] == 0:
+            raise ValueError("Cannot get first frame as input image, please specify --image parameter")   # INFER:214-215
+        first = Image.fromarray(images_u8[0].cpu().numpy(), "RGB")
+    if num_frames is not None:
+        images_u8, masks_u8 = images_u8[:num_frames], masks_u8[:num_frames]
+    if max_area is None:
+        max_area = 480 * 832 if model == "480p" else 720 * 1280
+    h, w = target_size(first.height, first.width, max_area) if size is None else (int(size[0]), int(size[1]))
+    image = first.resize((w, h))
+    frame_table, mask_table = (torch.from_numpy(t).to(dev) for t in resample.u8_to_f32_tables())
+    video_ref = ops.u8_lut_planar(ops.resample_u8(images_u8.contiguous(), (h, w)), frame_table).unsqueeze(0)
+    m32 = ops.u8_lut_planar(ops.resample_u8(masks_u8.contiguous(), (h, w)), mask_table)[0]
+    if soften:
+        m32 = ops.soften_mask(m32.contiguous(), transition_distance, decay_type)
+    return image, video_ref, m32.unsqueeze(0).unsqueeze(0), h, w
+
+
 def save_png_frames(frames, output_path: str) -> str:
     """INFER:323-339 (`--save-png`): frames [F,H,W,3] (float in [0,1] or uint8, numpy / torch / a list of PIL images) -> PNG files
     `<output stem>_frames/frame_0000.png ...`; float frames are quantised as the reference does, `(x * 255).clip(0, 255).astype(uint8)`

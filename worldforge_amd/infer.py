@@ -1,6 +1,7 @@
 """The entry point of the hot path: `python -m worldforge_amd.infer ...` = the reference's `infer_worldforge.py` (INFER:153-339) on this engine.
 
     INFER:153-156  read the warped frames / masks of --video-ref            -> harness.read_frames_from_directory
+                   or --stage1 vggt / depthcrafter: stage 1 in this process  -> stage1.py, harness.prepare_inputs_device (no files between)
     INFER:158-202  model folder, VAE fp32, pipeline bf16, clean scheduler   -> AutoencoderKLWan / WanTransformer3DModel.from_pretrained (own
                                                                                safetensors reader, checkpoint.py), UniPCMultistepScheduler.from_config
     INFER:206-254  size rule, frame / mask resize, optional mask softening  -> harness.prepare_inputs (wf_soften_mask on the device)
@@ -100,10 +101,18 @@ def run(models_dir: Optional[str], video_ref: str, model: str = "720p", output: 
         use_pca_channel_selection: bool = False, soften_mask: bool = False, transition_distance: int = 15, decay_type: str = "sine",
         save_png: bool = False, device: str = "cuda:0", components: Optional[dict] = None, max_area: Optional[int] = None, seed: int = 42,
         vae_precision: str = "fp16x3", flow_backend: str = "farneback", dit_precision: str = "bf16", text_encoder: str = "transformers",
-        image_encoder: str = "transformers"):
+        image_encoder: str = "transformers", stage1: str = "files", stage1_frames=None, save_stage1: Optional[str] = None,
+        **stage1_options):
     """INFER:153-339.  Returns (frames float32 [F,H,W,3] in [0,1], output directory of the PNG frames or None).
     components: {"transformer", "vae", "scheduler"} to use instead of loading `models_dir` (tests; synthetic weights); max_area overrides the
-    model's pixel budget the same way harness.prepare_inputs documents."""
+    model's pixel budget the same way harness.prepare_inputs documents.
+    stage1 "vggt" / "depthcrafter" (video_ref None): stage 1 runs in this process BEFORE the DiT and the VAE are loaded, its options come
+    as keywords under the stage-1 commands' own names (vggt_checkpoint, image_path, direction, ... / video_path, depth_npz, ...; see
+    stage1.py), and its frames reach the sampler through harness.prepare_inputs_device without leaving the device; save_stage1 also writes
+    them as PNG files.  stage1_frames = (images u8 [F,H,W,3], masks u8 [F,H,W] 0 / 1) hands over tensors a caller already holds.  The
+    tensors are bit-identical to the file route's.  Stated deviation: the in-process route keeps stage 1's frame order; the file route
+    sorts the file names, which is the same order for fewer than 100 frames and label angles below 100 degrees."""
+    from . import stage1 as stage1_mod
     from .dit import WanTransformer3DModel
     from .pipeline import WanImageToVideoPipeline
     from .scheduler import UniPCMultistepScheduler
@@ -114,6 +123,18 @@ def run(models_dir: Optional[str], video_ref: str, model: str = "720p", output: 
     if image_encoder not in ("transformers", "native"):
         raise ValueError(f"--image-encoder {image_encoder!r}: transformers or native")
     dev = torch.device(device)
+    eff_frames = max(num_frames // 4 * 4 + 1 if num_frames % 4 != 1 else num_frames, 1)     # PIPE:475-478
+    mismatch = ("{src} holds {n} frames but --num-frames {num} decodes {eff}: the reference blends "
+                "frame by frame (scheduling_unipc_multistep_clean.py:1326 raises on a mismatch)")
+    in_process = stage1 != "files" or stage1_frames is not None
+    if in_process:   # stage 1 first: VGGT and the DiT / VAE are never resident together, and a wrong frame count is refused before they load
+        images_u8, masks_u8 = stage1_mod.frames_for(stage1, stage1_options, eff_frames, dev, stage1_frames=stage1_frames, save_dir=save_stage1)
+        if images_u8.shape[0] != eff_frames:
+            raise ValueError(mismatch.format(src="stage1_frames" if stage1_frames is not None else f"--stage1 {stage1}", n=images_u8.shape[0], num=num_frames, eff=eff_frames))
+    elif stage1_options:
+        raise TypeError(f"--stage1 files does not take {sorted(stage1_options)}")
+    elif video_ref is None:
+        raise ValueError("--stage1 files needs --video-ref")
     model_path = None
     if components is None:
         model_path = os.path.join(models_dir, "wan2.1_480p_model_local" if model == "480p" else "wan2.1_720p_model_local")   # INFER:160-168
@@ -132,13 +153,15 @@ def run(models_dir: Optional[str], video_ref: str, model: str = "720p", output: 
     # --image given: the size rule takes the IMAGE's aspect ratio and the warped frames / masks are resized to it (INFER:209-241).  The
     # warped sequence is NOT truncated to --num-frames: the reference blends frame by frame and its resize of a sequence of another length
     # raises (scheduling_unipc_multistep_clean.py:1326), so a mismatch is an error here too, before any GPU work.
-    pil, video, mask, height, width = harness.prepare_inputs(video_ref, model=model, num_frames=None, soften=soften_mask,
-                                                             transition_distance=transition_distance, decay_type=decay_type, device=dev,
-                                                             max_area=max_area, image=image)
-    eff_frames = max(num_frames // 4 * 4 + 1 if num_frames % 4 != 1 else num_frames, 1)     # PIPE:475-478
+    prep = dict(model=model, num_frames=None, soften=soften_mask, transition_distance=transition_distance, decay_type=decay_type, device=dev,
+                max_area=max_area, image=image)
+    if in_process:
+        pil, video, mask, height, width = harness.prepare_inputs_device(images_u8, masks_u8, **prep)
+        del images_u8, masks_u8
+    else:
+        pil, video, mask, height, width = harness.prepare_inputs(video_ref, **prep)
     if video.shape[2] != eff_frames:
-        raise ValueError(f"--video-ref holds {video.shape[2]} frames but --num-frames {num_frames} decodes {eff_frames}: the reference blends "
-                         "frame by frame (scheduling_unipc_multistep_clean.py:1326 raises on a mismatch)")
+        raise ValueError(mismatch.format(src="--video-ref", n=video.shape[2], num=num_frames, eff=eff_frames))
     if negative_prompt is None:   # INFER:277-284: the two negative prompts are literals of the entry point, chosen by --static
         negative_prompt = NEGATIVE_PROMPT_STATIC if static else NEGATIVE_PROMPT_DYNAMIC
 
@@ -173,7 +196,7 @@ def main(argv=None):
     ap.add_argument("--models-dir", required=True)
     ap.add_argument("--output", default="output.mp4")
     ap.add_argument("--image", default=None)
-    ap.add_argument("--video-ref", required=True)
+    ap.add_argument("--video-ref", default=None, help="the warped frames / masks of a stage-1 command (required with --stage1 files)")
     ap.add_argument("--guided", action="store_true")
     ap.add_argument("--resample-steps", type=int, default=3)
     ap.add_argument("--guide-steps", type=int, default=20)
@@ -201,14 +224,19 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--dit-precision", choices=["bf16", "mxfp8"], default="bf16",
                     help="DiT block linears: bf16 (default) or the opt-in MX-fp8 GEMMs (lower precision, faster)")
+    from . import stage1 as stage1_mod
+    stage1_mod.add_arguments(ap)
     a = ap.parse_args(argv)
+    if a.stage1 == "files" and a.video_ref is None:
+        ap.error("--stage1 files needs --video-ref")
     frames, png_dir = run(a.models_dir, a.video_ref, model=a.model, output=a.output, image=a.image, guided=a.guided,
                           resample_steps=a.resample_steps, guide_steps=a.guide_steps, omega=a.omega, omega_resample=a.omega_resample,
                           num_frames=a.num_frames, num_inference_steps=a.num_inference_steps, guidance_scale=a.guidance_scale,
                           resample_round=a.resample_round, static=a.static == "True", prompt=a.prompt, negative_prompt=a.negative_prompt,
                           embeds=a.embeds, use_pca_channel_selection=a.use_pca_channel_selection, soften_mask=a.soften_mask,
                           transition_distance=a.transition_distance, decay_type=a.decay_type, save_png=a.save_png, device=a.device,
-                          dit_precision=a.dit_precision, text_encoder=a.text_encoder, image_encoder=a.image_encoder)
+                          dit_precision=a.dit_precision, text_encoder=a.text_encoder, image_encoder=a.image_encoder,
+                          stage1=a.stage1, save_stage1=a.save_stage1, **stage1_mod.options_from_args(a))
     print(f"{len(frames)} frames -> {png_dir}")
 
 

@@ -5,7 +5,8 @@ cache, and the block-sparse 720p refine pass with switched LoRAs, all on ONE res
     RUN:203-226  tokenizer, UMT5, VAE bf16, scheduler, DiT bf16; the distill LoRA  -> LongCatVideoPipeline.from_pretrained (own safetensors reader,
                                                                                       header check before upload, bf16-first rule), dit.load_lora / enable_loras
     RUN:231-282  warped frames / masks, the input image, size, optional softening  -> harness.read_frames_from_directory / prepare_inputs (wf_soften_mask
-                                                                                      on the device)
+                                                                                      on the device); or --stage1 vggt / depthcrafter: stage 1 in this
+                                                                                      process (stage1.py) and harness.prepare_inputs_device, no files between
     RUN:284-332  prompts, CPU generator seeded --seed                              -> --embeds, or the folder's tokenizer / text_encoder run once and freed
     RUN:362-385  pipe.generate_i2v(...)                                            -> LongCatVideoPipeline.generate_i2v
     (engine)     --extend-windows N                                                -> N x generate_vc on the previous window's last --num-cond-frames frames
@@ -162,10 +163,17 @@ def run(checkpoint_dir: Optional[str], video_ref: str, output: str = "output_i2v
         upscale_height: int = 704, upscale_width: int = 1280, refine_num_inference_steps: int = 50, extend_windows: int = 0,
         num_cond_frames: int = 13, no_kv_cache: bool = False, refine_kv_cache: bool = False, context_parallel_size: int = 1,
         device: str = "cuda:0", dit_precision: str = "bf16", vae_precision: str = "bf16", flow_backend: str = "farneback",
-        components: Optional[dict] = None, text_encoder: str = "transformers") -> LongCatRun:
+        components: Optional[dict] = None, text_encoder: str = "transformers", stage1: str = "files", stage1_frames=None,
+        save_stage1: Optional[str] = None, **stage1_options) -> LongCatRun:
     """RUN:170-500 plus the continuation chain; see the module docstring.  components: any of {"vae", "scheduler", "dit"} to use
     instead of loading it from `checkpoint_dir` (tests: a synthetic DiT folder beside an injected VAE).  refine_num_inference_steps:
-    the reference's fixed 50 (RUN:484), a keyword here so that the chain can be exercised at test sizes."""
+    the reference's fixed 50 (RUN:484), a keyword here so that the chain can be exercised at test sizes.
+    stage1 "vggt" / "depthcrafter" (video_ref None), stage1_frames, save_stage1 and the stage-1 options as keywords: as
+    worldforge_amd.infer.run -- stage 1 runs in this process before UMT5, the DiT and the VAE are loaded and its frames reach the sampler
+    through harness.prepare_inputs_device, bit-identical to the file route's.  Stated deviation: the in-process route keeps stage 1's
+    frame order; the file route sorts the file names, which is the same order for fewer than 100 frames and label angles below 100
+    degrees."""
+    from . import stage1 as stage1_mod
     from .longcat_pipeline import LongCatVideoPipeline
 
     # ---- everything that can be refused without a device --------------------------------------------------------------------------
@@ -185,10 +193,23 @@ def run(checkpoint_dir: Optional[str], video_ref: str, output: str = "output_i2v
             lora_files[key] = os.path.join(checkpoint_dir, "lora", key + ".safetensors")
             if not os.path.isfile(lora_files[key]):
                 raise ValueError(f"LoRA file does not exist: {lora_files[key]}")
-    warped, _, first_frame = harness.read_frames_from_directory(video_ref)
     eff_frames = max(num_frames // 4 * 4 + 1 if num_frames % 4 != 1 else num_frames, 1)     # PIPE:700-704
-    if len(warped) != eff_frames:
-        raise ValueError(f"--video-ref holds {len(warped)} frames but --num-frames {num_frames} decodes {eff_frames}: the reference blends "
+    in_process = stage1 != "files" or stage1_frames is not None
+    if in_process:   # the one step up here that needs the device: stage 1 itself, before anything else is loaded
+        from PIL import Image
+        images_u8, masks_u8 = stage1_mod.frames_for(stage1, stage1_options, eff_frames, torch.device(device), stage1_frames=stage1_frames,
+                                                    save_dir=save_stage1)
+        n_warped, source = images_u8.shape[0], "stage1_frames" if stage1_frames is not None else f"--stage1 {stage1}"
+        first_frame = Image.fromarray(images_u8[0].cpu().numpy(), "RGB") if n_warped else None
+    elif stage1_options:
+        raise TypeError(f"--stage1 files does not take {sorted(stage1_options)}")
+    elif video_ref is None:
+        raise ValueError("--stage1 files needs --video-ref")
+    else:
+        warped, _, first_frame = harness.read_frames_from_directory(video_ref)
+        n_warped, source = len(warped), "--video-ref"
+    if n_warped != eff_frames:
+        raise ValueError(f"{source} holds {n_warped} frames but --num-frames {num_frames} decodes {eff_frames}: the reference blends "
                          "frame by frame")
     if image is not None:
         from PIL import Image
@@ -231,9 +252,13 @@ def run(checkpoint_dir: Optional[str], video_ref: str, output: str = "output_i2v
         dit.enable_loras(["cfg_step_lora"])
 
     # ---- inputs (RUN:231-282) -------------------------------------------------------------------------------------------------------
-    pil, video, mask, height, width = harness.prepare_inputs(video_ref, model=resolution, num_frames=None, soften=soften_mask,
-                                                             transition_distance=transition_distance, decay_type=decay_type, device=dev,
-                                                             image=image, size=(height, width))
+    prep = dict(model=resolution, num_frames=None, soften=soften_mask, transition_distance=transition_distance, decay_type=decay_type,
+                device=dev, image=image, size=(height, width))
+    if in_process:
+        pil, video, mask, height, width = harness.prepare_inputs_device(images_u8, masks_u8, **prep)
+        del images_u8, masks_u8
+    else:
+        pil, video, mask, height, width = harness.prepare_inputs(video_ref, **prep)
     # ---- stage 1 (RUN:328-385) -------------------------------------------------------------------------------------------------------
     generator = torch.Generator(device="cpu")
     generator.manual_seed(seed)
@@ -285,7 +310,7 @@ def run(checkpoint_dir: Optional[str], video_ref: str, output: str = "output_i2v
     return result
 
 
-def build_parser() -> argparse.ArgumentParser:
+def build_parser(video_ref_required: bool = True) -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m worldforge_amd.longcat_infer",
                                  description="WorldForge LongCat-Video guided image-to-video, continuation and 720p refine on MI355X "
                                              "(the reference's run_longcat_worldforge_single.py arguments)")
@@ -294,7 +319,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--context_parallel_size", type=int, default=1, help="must be 1")
     ap.add_argument("--enable_compile", action="store_true", help="accepted and ignored")
     ap.add_argument("--use_distill", action="store_true")
-    ap.add_argument("--video-ref", required=True)
+    ap.add_argument("--video-ref", required=video_ref_required, default=None)
     ap.add_argument("--image", default=None)
     ap.add_argument("--prompt", default=None)
     ap.add_argument("--scene", default=None, help="accepted and ignored: the reference's scene -> prompt table is not shipped, pass --prompt")
@@ -340,8 +365,11 @@ def build_parser() -> argparse.ArgumentParser:
 
 def cli_parser() -> argparse.ArgumentParser:
     """build_parser() (the reference's arguments and the engine's own, pinned as a set by tests/test_longcat_checkpoint.py) plus
-    --text-encoder: what the command line parses."""
-    ap = build_parser()
+    --text-encoder and the in-process stage 1 (--stage1, --save-stage1 and the stage-1 commands' options, stage1.py): what the command
+    line parses."""
+    from . import stage1 as stage1_mod
+    ap = build_parser(video_ref_required=False)   # --video-ref is required only with --stage1 files (main checks that)
+    stage1_mod.add_arguments(ap)
     ap.add_argument("--text-encoder", choices=["transformers", "native"], default="transformers",
                     help="without --embeds: run the folder's UMT5 through the Hugging Face class (default) or on this engine's own kernels "
                          "(worldforge_amd/umt5.py; the tokenizer still comes from transformers)")
@@ -349,7 +377,11 @@ def cli_parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None):
-    a = cli_parser().parse_args(argv)
+    from . import stage1 as stage1_mod
+    ap = cli_parser()
+    a = ap.parse_args(argv)
+    if a.stage1 == "files" and a.video_ref is None:
+        ap.error("--stage1 files needs --video-ref")
     for flag, on in (("--enable_compile", a.enable_compile), ("--fps", a.fps != 15), ("--scene", a.scene is not None)):
         if on:
             print(f"note: {flag} is accepted and ignored" + (" (pass --prompt)" if flag == "--scene" else ""))
@@ -362,7 +394,7 @@ def main(argv=None):
             enable_upscale=a.enable_upscale, t_thresh=a.t_thresh, upscale_height=a.upscale_height, upscale_width=a.upscale_width,
             extend_windows=a.extend_windows, num_cond_frames=a.num_cond_frames, no_kv_cache=a.no_kv_cache, refine_kv_cache=a.refine_kv_cache,
             context_parallel_size=a.context_parallel_size, device=a.device, dit_precision=a.dit_precision, vae_precision=a.vae_precision,
-            text_encoder=a.text_encoder)
+            text_encoder=a.text_encoder, stage1=a.stage1, save_stage1=a.save_stage1, **stage1_mod.options_from_args(a))
     print(f"{len(r.frames)} frames -> {r.png_dir}")
     if r.refined is not None:
         print(f"{len(r.refined)} refined frames -> {r.refined_png_dir}")

@@ -254,6 +254,65 @@ def soften_mask(mask: torch.Tensor, transition_distance: int = 15, decay_type: s
     return out
 
 
+_RESAMPLE_TABLES: dict = {}
+
+
+def _resample_tables(n_in: int, n_out: int, device):
+    """Pillow's tables of one axis on `device` (bounds, coefs, ksize), built and checked once per (in, out, device): they are read-only."""
+    from . import resample
+    key = (n_in, n_out, str(device))
+    if key not in _RESAMPLE_TABLES:
+        bounds, coefs = resample.pil_resample_tables(n_in, n_out)
+        if bounds[:, 0].min() < 0 or bounds[:, 1].min() < 1 or (bounds[:, 0] + bounds[:, 1]).max() > n_in or bounds[:, 1].max() > coefs.shape[1]:
+            raise ValueError(f"resample tables {n_in} -> {n_out}: a tap window leaves the axis")   # the C entry trusts what it is handed
+        if len(_RESAMPLE_TABLES) >= 64:
+            _RESAMPLE_TABLES.clear()
+        _RESAMPLE_TABLES[key] = (torch.from_numpy(bounds).to(device), torch.from_numpy(coefs).to(device), coefs.shape[1])
+    return _RESAMPLE_TABLES[key]
+
+
+def resample_u8(frames: torch.Tensor, size_hw) -> torch.Tensor:
+    """`PIL.Image.resize((W, H))` (bicubic, Pillow's default for modes RGB and L) of every frame, bit for bit, on the device
+    (wf_resample_u8): frames u8 [T, h, w, C] (C = 1 or 3) or [T, h, w] -> u8 of the same rank at H x W.  Pillow's coefficient tables
+    are built here on the host (resample.pil_resample_tables; kept per size pair) and uploaded, so the kernel only ever reads tables whose taps lie inside
+    the image."""
+    frames = _dev(frames)
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4):
+        raise TypeError(f"resample_u8: uint8 [T, h, w, C] or [T, h, w], got {frames.dtype} {tuple(frames.shape)}")
+    planar = frames.dim() == 3
+    T, h, w = frames.shape[:3]
+    C = 1 if planar else frames.shape[3]
+    H, W = int(size_hw[0]), int(size_hw[1])
+    if C not in (1, 3) or min(T, h, w, H, W) <= 0:
+        raise ValueError(f"resample_u8: {tuple(frames.shape)} -> {(H, W)}: sizes must be positive and C 1 or 3")
+    dev = frames.device
+    tabs = []
+    for n_in, n_out in ((w, W), (h, H)):
+        if n_in == n_out:
+            tabs += [None, None, 0]
+            continue
+        tabs += list(_resample_tables(n_in, n_out, dev))
+    out = torch.empty((T, H, W) if planar else (T, H, W, C), dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(_ffi.lib().wf_resample_u8_workspace_bytes(T, h, w, H, W, C)), dtype=torch.uint8, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    call("wf_resample_u8", frames.data_ptr(), out.data_ptr(), T, h, w, H, W, C, ptr(tabs[0]), ptr(tabs[1]), tabs[2], ptr(tabs[3]),
+         ptr(tabs[4]), tabs[5], ws.data_ptr(), stream())
+    return out
+
+
+def u8_lut_planar(frames: torch.Tensor, lut: torch.Tensor) -> torch.Tensor:
+    """frames u8 [T, h, w, C] or [T, h, w], lut f32 [256] -> f32 [C, T, h, w] = lut[frames] (wf_u8_lut_planar_f32): the u8 -> f32 step
+    of harness.prepare_inputs with the host's own 256 values, channels moved in front."""
+    frames, lut = _dev(frames), _dev(lut)
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or lut.dtype != torch.float32 or lut.numel() != 256:
+        raise TypeError("u8_lut_planar: uint8 [T, h, w, C] or [T, h, w] and a float32 table of 256 entries")
+    T, h, w = frames.shape[:3]
+    C = 1 if frames.dim() == 3 else frames.shape[3]
+    out = torch.empty((C, T, h, w), dtype=torch.float32, device=frames.device)
+    call("wf_u8_lut_planar_f32", frames.data_ptr(), lut.data_ptr(), out.data_ptr(), T, h, w, C, stream())
+    return out
+
+
 def farneback_flows(x: torch.Tensor, quant_mode: int = 0) -> torch.Tensor:
     """SCHED:156-248 for every channel at once: x [C,T,h,w] (f32 / bf16) -> flows [C,T-1,2,h,w] fp32 (device).
     quant_mode 0 = the Wan scheduler's uint8 preparation (one global range), 1 = the LongCat scheduler's (a range per channel)."""

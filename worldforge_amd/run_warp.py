@@ -20,10 +20,8 @@ import numpy as np
 DIRECTIONS = ["up", "down", "left", "right", "forward", "backward"]
 
 
-def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="python -m worldforge_amd.run_warp", description="Single-View Warping with VGGT")
-    p.add_argument("--image_path", type=str, required=True, help="Path to input image directory")
-    p.add_argument("--output_path", type=str, default="output_warp", help="Path to output directory")
+def add_arguments(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
+    """The warp options (run_warp.py's names, defaults and choices), for this command's parser and for any other that carries them."""
     p.add_argument("--camera", type=int, default=0, help="Camera index for single-view warping")
     p.add_argument("--direction", type=str, default="right", choices=DIRECTIONS,
                    help="Camera motion direction: up/down/left/right (orbit around focus point), forward/backward (dolly)")
@@ -40,6 +38,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--depth_segments", type=int, default=8, help="Number of depth segments for layered crack filling")
     p.add_argument("--outlier_min_neighbors", type=int, default=10, help="Minimum neighbors to keep a pixel (fewer = outlier)")
     p.add_argument("--outlier_neighbor_radius", type=int, default=3, help="Search radius for counting neighbors")
+    return p
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m worldforge_amd.run_warp", description="Single-View Warping with VGGT")
+    p.add_argument("--image_path", type=str, required=True, help="Path to input image directory")
+    p.add_argument("--output_path", type=str, default="output_warp", help="Path to output directory")
+    add_arguments(p)
     p.add_argument("--checkpoint", type=str, required=True, help="VGGT checkpoint folder: model.safetensors (+ optional config.json)")
     p.add_argument("--device", type=str, default="cuda:0")
     return p
@@ -109,15 +115,17 @@ def save_warped_results(images, masks, infos, output_folder: str, camera_idx: in
     return folder
 
 
-def main(argv: Optional[List[str]] = None) -> int:
+def warp_frames(args, device=None):
+    """run_warp.py:199-300 without the files: validated arguments (image_path, checkpoint, the warp options; `device` overrides
+    args.device) -> (images u8 [F, H, W, 3], masks u8 [F, H, W] (0 / 1), infos), the tensors on the device.  args.camera is set to the
+    camera actually used.  The VGGT model lives only inside this call."""
     import torch
     from PIL import Image
 
     from . import vggt, warp
-    args = validate_args(build_parser().parse_args(argv))
-    os.makedirs(args.output_path, exist_ok=True)
+    device = args.device if device is None else device
     print("Loading VGGT model...")
-    model = vggt.VGGT.from_pretrained(args.checkpoint, device=args.device, depth=True)
+    model = vggt.VGGT.from_pretrained(args.checkpoint, device=device, depth=True)
     names = load_images_from_path(args.image_path)
     if args.camera >= len(names):
         print(f"Warning: camera index {args.camera} out of range, using 0")
@@ -136,13 +144,19 @@ def main(argv: Optional[List[str]] = None) -> int:
     oh, ow = original.shape[:2]
     depth, conf, K = vggt.to_image_size(r["depth"][0, idx], r["depth_conf"][0, idx], r["intrinsic"][0, idx], tuple(x.shape[-2:]), (oh, ow))
     print(f"Warping camera {idx} in {args.direction} direction...")
-    images, masks, infos = warp.warp_single_img(
+    return warp.warp_single_img(
         extrinsic=r["extrinsic"][0, idx].double().cpu().numpy(), intrinsic=K.double().cpu().numpy(),
         image=torch.from_numpy(original.transpose(2, 0, 1)).float(), depth_map=depth.squeeze(-1), depth_conf=conf,
         direction=args.direction, degree=args.degree, conf_threshold=args.conf_single, frame_num=args.frame_single,
         fill_cracks=args.fill_cracks, crack_params=warp.crack_params_from_args(args), look_at_depth=args.look_at_depth,
-        depth_segments=args.depth_segments, device=args.device)
-    save_warped_results(images.cpu().numpy(), masks.cpu().numpy(), infos, args.output_path, idx, args)
+        depth_segments=args.depth_segments, device=device)
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    args = validate_args(build_parser().parse_args(argv))
+    os.makedirs(args.output_path, exist_ok=True)
+    images, masks, infos = warp_frames(args)
+    save_warped_results(images.cpu().numpy(), masks.cpu().numpy(), infos, args.output_path, args.camera, args)
     print(f"\nComplete! Results saved to: {args.output_path}")
     return 0
 

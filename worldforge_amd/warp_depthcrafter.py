@@ -35,6 +35,25 @@ NO_DEPTH = ("no depth file: give --depth_npz PATH or put depth.npz into {folder}
 NO_VIDEO = "--video_path {path} is not a folder: video files are not read here (no decoder); extract the frames into a folder of images."
 
 
+def add_arguments(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
+    """The warp options (the reference's names, defaults and choices, plus --no_antialias), for this command's parser and for any other
+    that carries them."""
+    p.add_argument("--direction", type=str, choices=["up", "down", "left", "right"], default="left", help="Warping direction")
+    p.add_argument("--degree", type=float, default=15, help="Warping angle in degrees")
+    p.add_argument("--look_at_depth", type=float, default=1.0, help="Look at depth multiplier")
+    p.add_argument("--zoom", type=str, choices=["zoom_in", "zoom_out", "none"], default="none", help="Zoom mode")
+    p.add_argument("--rate", type=float, default=0.8, help="Zoom rate (0.0-1.0)")
+    p.add_argument("--stable", action="store_true", help="Enable stable warping (complete transformation in first N frames)")
+    p.add_argument("--stable_frame", type=int, default=17, help="Number of frames to complete stable transformation (default: 17)")
+    p.add_argument("--enable_edge_filter", action="store_true", help="Enable depth edge filtering to reduce warping artifacts")
+    p.add_argument("--edge_threshold", type=float, default=0.1, help="Edge detection threshold (0.0-1.0)")
+    p.add_argument("--edge_dilation", type=int, default=3, help="Edge region dilation in pixels")
+    p.add_argument("--depth_jump_threshold", type=float, default=0.3, help="Depth discontinuity threshold")
+    p.add_argument("--neighbor_check_radius", type=int, default=2, help="Neighbor depth check radius")
+    p.add_argument("--no_antialias", action="store_true", help="Resize as torchvision releases before 0.17 do (no antialiasing)")
+    return p
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m worldforge_amd.warp_depthcrafter", description="DepthCrafter + 3D Warping Pipeline")
     p.add_argument("--video_path", type=str, required=True, help="Input image sequence directory")
@@ -52,20 +71,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=42, help="(compatibility only) Random seed")
     p.add_argument("--cpu_offload", type=str, default="model", choices=["model", "sequential", "none"],
                    help="(compatibility only) CPU offload mode")
-    p.add_argument("--direction", type=str, choices=["up", "down", "left", "right"], default="left", help="Warping direction")
-    p.add_argument("--degree", type=float, default=15, help="Warping angle in degrees")
-    p.add_argument("--look_at_depth", type=float, default=1.0, help="Look at depth multiplier")
-    p.add_argument("--zoom", type=str, choices=["zoom_in", "zoom_out", "none"], default="none", help="Zoom mode")
-    p.add_argument("--rate", type=float, default=0.8, help="Zoom rate (0.0-1.0)")
-    p.add_argument("--stable", action="store_true", help="Enable stable warping (complete transformation in first N frames)")
-    p.add_argument("--stable_frame", type=int, default=17, help="Number of frames to complete stable transformation (default: 17)")
-    p.add_argument("--enable_edge_filter", action="store_true", help="Enable depth edge filtering to reduce warping artifacts")
-    p.add_argument("--edge_threshold", type=float, default=0.1, help="Edge detection threshold (0.0-1.0)")
-    p.add_argument("--edge_dilation", type=int, default=3, help="Edge region dilation in pixels")
-    p.add_argument("--depth_jump_threshold", type=float, default=0.3, help="Depth discontinuity threshold")
-    p.add_argument("--neighbor_check_radius", type=int, default=2, help="Neighbor depth check radius")
+    add_arguments(p)
     p.add_argument("--depth_npz", type=str, default=None, help="depth.npz (key `depth`, [T, H, W]) to use instead of OUT/depth_estimation/<name>")
-    p.add_argument("--no_antialias", action="store_true", help="Resize as torchvision releases before 0.17 do (no antialiasing)")
     p.add_argument("--device", type=str, default="cuda:0")
     return p
 
@@ -115,8 +122,9 @@ def save_frames(images, masks, folder: str) -> str:
     return folder
 
 
-def main(argv: Optional[List[str]] = None) -> int:
-    args = build_parser().parse_args(argv)
+def warp_frames(args, device=None):
+    """:371-429 and :140-291 without the output files: parsed arguments (video_path, depth_npz / output_path, the warp options;
+    `device` overrides args.device) -> (images u8 [T, H, W, 3], masks u8 [T, H, W] (0 / 1), infos), the tensors on the device."""
     if args.zoom != "none" and not (0.0 < args.rate <= 1.0):
         raise ValueError(f"Rate must be between 0.0 and 1.0, got {args.rate}")
     names = list_frames(args.video_path)
@@ -128,11 +136,16 @@ def main(argv: Optional[List[str]] = None) -> int:
         raise ValueError(f"{frames.shape[0]} images in {args.video_path} but {depth.shape[0]} depth maps in {depth_path}")
     from . import warp
     print(f"Warping {frames.shape[0]} frames...")
-    images, masks, _ = warp.warp_depthcrafter_frames(
+    return warp.warp_depthcrafter_frames(
         frames, depth, direction=args.direction, degree=args.degree, look_at_depth=args.look_at_depth, zoom=args.zoom, rate=args.rate,
         stable=args.stable, stable_frame=args.stable_frame, enable_edge_filter=args.enable_edge_filter, edge_threshold=args.edge_threshold,
         edge_dilation=args.edge_dilation, depth_jump_threshold=args.depth_jump_threshold, neighbor_check_radius=args.neighbor_check_radius,
-        antialias=not args.no_antialias, device=args.device)
+        antialias=not args.no_antialias, device=args.device if device is None else device)
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    args = build_parser().parse_args(argv)
+    images, masks, _ = warp_frames(args)
     folder = save_frames(images.cpu().numpy(), masks.cpu().numpy(), os.path.join(args.output_path, "warped", "imgs"))
     print(f"\nWarping completed!\nResults saved to: {folder}")
     return 0
