@@ -707,6 +707,21 @@ int wf_resize_bilinear_aa_f32(const float* in, float* out, int T, int h, int w, 
 size_t wf_resample_u8_workspace_bytes(int T, int h, int w, int H, int W, int C);
 int wf_resample_u8(const uint8_t* in, uint8_t* out, int T, int h, int w, int H, int W, int C, const int32_t* xbounds, const int32_t* xcoefs,
                    int xk, const int32_t* ybounds, const int32_t* ycoefs, int yk, void* workspace, void* stream);
+/* A window of wf_resample_u8's result, looked up and planar, without the frames in between: in u8 [T][h][w][C] (C = 1 or 3) -> out f32
+ * [T][C][Hc][Wc] = lut[c][R[t][y0 + i][x0 + j][c]], R = what wf_resample_u8 writes for H x W with the same tables (both passes are
+ * independent per pixel, so the window alone is exact).  lut f32 [C][256] and the tables on the device; the tables are the WHOLE axes'
+ * (W and H rows) and trusted as for wf_resample_u8, and the row table must be one built for h -> H with taps no further than (yk - 1) / 2
+ * from (i + 0.5) h / H, as resample.filter_tables builds it: the column pass covers the source rows such a window can tap (rows outside
+ * them are read from the workspace as they lie there).  Column pass (w != W): the window's columns of those rows into a u8 intermediate
+ * in the workspace, as Pillow rounds between the passes; then one kernel runs the row taps (int32 sum from 1 << 21, >> 22, clamp), the
+ * look-up and the planar store.  w == W: no column pass, the kernel reads `in` at column x0 (workspace may be NULL); h == H: one tap per
+ * row; both: a windowed look-up.  The bytes do not depend on the grid.  Refused (WF_EINVAL) before any launch: a size <= 0, C not 1 or
+ * 3, a window that leaves H x W, a null in / out / lut, a pass without its tables or with k <= 0, a column pass without the workspace.
+ * workspace: wf_resample_u8_window_f32_workspace_bytes(...) bytes (0 for arguments the entry refuses). */
+size_t wf_resample_u8_window_f32_workspace_bytes(int T, int h, int w, int H, int W, int C, int y0, int x0, int Hc, int Wc);
+int wf_resample_u8_window_f32(const uint8_t* in, float* out, int T, int h, int w, int H, int W, int C, int y0, int x0, int Hc, int Wc,
+                              const int32_t* xbounds, const int32_t* xcoefs, int xk, const int32_t* ybounds, const int32_t* ycoefs, int yk,
+                              const float* lut, void* workspace, void* stream);
 /* 8-bit channels-last frames through a 256-entry table into planar floats: in u8 [T][h][w][C], lut f32 [256] (device) -> out f32
  * [C][T][h][w], out = lut[in].  The table carries the host's own u8 -> f32 expression, so no division runs on the device. */
 int wf_u8_lut_planar_f32(const uint8_t* in, const float* lut, float* out, int T, int h, int w, int C, void* stream);

@@ -18,7 +18,8 @@ fp32-input MFMA (csrc/clip.hip), the residual stream, the LayerNorms and the sof
     x   += wf_gemm_f32(h, fc2, bias)             WF_EPI_F32_ACC
 
 `hidden_states[-2]` is the residual stream after num_hidden_layers - 1 layers, without `post_layernorm`: the last layer and the final
-norm are checked in the checkpoint and never uploaded.  `preprocess` restates CLIPImageProcessor's PIL path on the host (once per video).
+norm are checked in the checkpoint and never uploaded.  `preprocess` restates CLIPImageProcessor's PIL path on the host; `preprocess_device`
+gives the same bits on the device (ops.resample_u8_window) and is what `encode_image` uses.
 Not built: position interpolation (the image must have the configured size), batches, the text tower, the projection heads.
 """
 from __future__ import annotations
@@ -284,14 +285,8 @@ def _raise_on(keep: Dict[str, dict], cfg: CLIPVisionConfig, where: str, dropped:
 _PIL_RESAMPLE = {0: "NEAREST", 1: "LANCZOS", 2: "BILINEAR", 3: "BICUBIC", 4: "BOX", 5: "HAMMING"}
 
 
-def preprocess(image, processor_config: dict) -> torch.Tensor:
-    """A PIL image -> pixel_values fp32 [3, S, S] as CLIPImageProcessor's PIL path computes them (image_processor/preprocessor_config.json):
-    convert to RGB, resize the shortest edge on the uint8 image with the configured PIL filter (the long edge is int(size * long / short)),
-    centre crop, uint8 -> float64 * rescale_factor -> float32, (x - mean) / std in float32.  Settings this does not implement raise
-    NotImplementedError: any of the five steps switched off, padding, a size that is not a shortest edge (or square), a crop larger
-    than the resized image."""
-    from PIL import Image
-    c = processor_config
+def _processor_settings(c: dict):
+    """The checks of preprocess / preprocess_device on a preprocessor_config -> (shortest edge, crop S, resample code, mean, std, rescale)."""
     for flag in ("do_resize", "do_center_crop", "do_rescale", "do_normalize"):
         if not c.get(flag, True):
             raise NotImplementedError(f"preprocessor_config {flag}=false is not implemented")
@@ -313,31 +308,77 @@ def preprocess(image, processor_config: dict) -> torch.Tensor:
     mean, std = c.get("image_mean"), c.get("image_std")
     if mean is None or std is None or len(mean) != 3 or len(std) != 3:
         raise NotImplementedError("preprocessor_config needs image_mean and image_std of 3 values")
+    return size["shortest_edge"], int(crop["height"]), resample, mean, std, float(c.get("rescale_factor", 1 / 255))
+
+
+def _resized_and_window(w: int, h: int, shortest_edge, S: int):
+    """The shortest-edge rule and the centre crop: (nw, nh, top, left)."""
+    short, long = (w, h) if w <= h else (h, w)
+    new_short, new_long = int(shortest_edge), int(shortest_edge * long / short)
+    nw, nh = (new_short, new_long) if w <= h else (new_long, new_short)
+    if nh < S or nw < S:
+        raise NotImplementedError(f"crop {S} is larger than the resized image {nw} x {nh}: padding is not implemented")
+    return nw, nh, (nh - S) // 2, (nw - S) // 2
+
+
+def _rescale_normalize(a: np.ndarray, rescale: float, mean, std) -> np.ndarray:
+    """uint8 [3, h, w] -> float32: float64 rescale rounded to float32, then (x - mean) / std in float32."""
+    x = (a.astype(np.float64) * rescale).astype(np.float32)
+    return ((x.T - np.array(mean, dtype=np.float32)) / np.array(std, dtype=np.float32)).T
+
+
+def preprocess(image, processor_config: dict) -> torch.Tensor:
+    """A PIL image -> pixel_values fp32 [3, S, S] as CLIPImageProcessor's PIL path computes them (image_processor/preprocessor_config.json):
+    convert to RGB, resize the shortest edge on the uint8 image with the configured PIL filter (the long edge is int(size * long / short)),
+    centre crop, uint8 -> float64 * rescale_factor -> float32, (x - mean) / std in float32.  Settings this does not implement raise
+    NotImplementedError: any of the five steps switched off, padding, a size that is not a shortest edge (or square), a crop larger
+    than the resized image."""
+    from PIL import Image
+    edge, S, resample, mean, std, rescale = _processor_settings(processor_config)
     if not isinstance(image, Image.Image):
         raise TypeError(f"preprocess takes a PIL image, got {type(image)}")
     img = image.convert("RGB")
-    w, h = img.size
-    short, long = (w, h) if w <= h else (h, w)
-    new_short, new_long = int(size["shortest_edge"]), int(size["shortest_edge"] * long / short)
-    nw, nh = (new_short, new_long) if w <= h else (new_long, new_short)
+    nw, nh, top, left = _resized_and_window(*img.size, edge, S)
     img = img.resize((nw, nh), resample=getattr(Image.Resampling, _PIL_RESAMPLE[resample]))
-    S = int(crop["height"])
-    if nh < S or nw < S:
-        raise NotImplementedError(f"crop {S} is larger than the resized image {nw} x {nh}: padding is not implemented")
-    top, left = (nh - S) // 2, (nw - S) // 2
     a = np.asarray(img)[top:top + S, left:left + S].transpose(2, 0, 1)
-    x = (a.astype(np.float64) * float(c.get("rescale_factor", 1 / 255))).astype(np.float32)
-    x = ((x.T - np.array(mean, dtype=np.float32)) / np.array(std, dtype=np.float32)).T
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    return torch.from_numpy(np.ascontiguousarray(_rescale_normalize(a, rescale, mean, std), dtype=np.float32))
+
+
+def preprocess_device(image, processor_config: dict, device) -> torch.Tensor:
+    """preprocess on the device, bit for bit: a PIL image or a u8 [h, w, 3] tensor (host or device) -> pixel_values fp32 [3, S, S] on
+    `device`.  The same settings and refusals (_processor_settings); the resize with the configured filter, the centre-crop window, the
+    u8 -> f32 step and the move to planar are one entry (ops.resample_u8_window) that computes the window only; the three per-channel
+    tables of 256 floats are preprocess' own two expressions on every byte value.  resample 0 (NEAREST is no convolution in Pillow) raises
+    NotImplementedError here; the host function serves it."""
+    from . import ops
+    edge, S, resample, mean, std, rescale = _processor_settings(processor_config)
+    if resample == 0:
+        raise NotImplementedError("preprocessor_config resample 0 (NEAREST) is not implemented on the device: use preprocess")
+    if isinstance(image, torch.Tensor):
+        if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3:
+            raise TypeError(f"preprocess_device takes a PIL image or a uint8 [h, w, 3] tensor, got {image.dtype} {tuple(image.shape)}")
+        px = image
+    else:
+        from PIL import Image
+        if not isinstance(image, Image.Image):
+            raise TypeError(f"preprocess_device takes a PIL image or a uint8 [h, w, 3] tensor, got {type(image)}")
+        px = torch.from_numpy(np.asarray(image.convert("RGB")).copy())
+    h, w = px.shape[:2]
+    nw, nh, top, left = _resized_and_window(w, h, edge, S)
+    table = np.broadcast_to(np.arange(256, dtype=np.uint8)[None, :, None], (3, 256, 1))
+    lut = torch.from_numpy(np.ascontiguousarray(_rescale_normalize(table, rescale, mean, std)[:, :, 0], dtype=np.float32))
+    out = ops.resample_u8_window(px.to(device).unsqueeze(0), (nh, nw), (top, left, S, S), lut.to(device), filter=_PIL_RESAMPLE[resample].lower())
+    return out[0]
 
 
 def encode_image(model_path: str, image, device, subfolder: Optional[str] = "image_encoder") -> torch.Tensor:
-    """PIPE:207-211 on this engine: the folder's `image_processor/preprocessor_config.json` and `image_encoder/`, a PIL image ->
-    image_embeds bf16 [1, tokens, hidden] (hidden_states[-2], cast once).  The encoder is built for the call and freed afterwards."""
+    """PIPE:207-211 on this engine: the folder's `image_processor/preprocessor_config.json` and `image_encoder/`, a PIL image or a u8
+    [h, w, 3] tensor (a frame that is already on the device stays there) -> image_embeds bf16 [1, tokens, hidden] (hidden_states[-2], cast
+    once).  The pixels go through preprocess_device.  The encoder is built for the call and freed afterwards."""
     with open(os.path.join(model_path, "image_processor", "preprocessor_config.json")) as f:
         pc = json.load(f)
     model = CLIPVisionModel.from_pretrained(model_path, device=device, subfolder=subfolder)
-    out = model(preprocess(image, pc)).to(torch.bfloat16).unsqueeze(0)
+    out = model(preprocess_device(image, pc, device)).to(torch.bfloat16).unsqueeze(0)
     del model
     if torch.device(device).type == "cuda":
         torch.cuda.empty_cache()

@@ -141,6 +141,71 @@ __global__ void __launch_bounds__(256) k_u8_lut_planar(const uint8_t* __restrict
   }
 }
 
+// The row pass of wf_resample_u8_window_f32, the table look-up and the move to planar floats in one kernel:
+//   out[t][c][oy][ox] = lut[c][clip8((1 << 21) + sum_j src[t][first_oy + j][xoff + ox][c] * coefs[oy][j])],  oy < Hc, ox < Wc,
+// src = the column pass's u8 intermediate or the input itself (fstride / rstride = bytes per frame / per row, xoff = the window's first
+// column in it); bounds == NULL is the skipped row pass: one tap of weight 1 on row y0 + oy.  bounds / coefs start at the window's first row.
+// A wavefront owns one output row (t, oy) at a time, so the tap window and the coefficients are wave-uniform (scalar loads), and walks the
+// row's C planes in ALIGNED groups of four floats: a plane row of Wc floats starts at any phase `a` of a 16-byte line, group g holds the
+// elements 4 g - a .. 4 g - a + 3, a lane computes one group and stores it whole, the clipped first and last group element by element.
+// The C tables of 256 floats sit in LDS.
+__global__ void __launch_bounds__(256) k_ru_window_lut(const uint8_t* __restrict__ src, size_t fstride, size_t rstride, int xoff, int y0,
+                                                       const int32_t* __restrict__ bounds, const int32_t* __restrict__ coefs, int ksize,
+                                                       const float* __restrict__ lut, float* __restrict__ out, int T, int C, int Hc,
+                                                       int Wc) {
+  __shared__ float s_lut[3 * 256];
+  for (int i = threadIdx.x; i < C * 256; i += 256) s_lut[i] = lut[i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const unsigned phase = (unsigned)(((uintptr_t)out >> 2) & 3);
+  const size_t rows = (size_t)T * Hc, step = (size_t)gridDim.x * 4;
+  for (size_t row0 = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); row0 < rows; row0 += step) {
+    const unsigned row_lo = __builtin_amdgcn_readfirstlane((unsigned)row0), row_hi = __builtin_amdgcn_readfirstlane((unsigned)(row0 >> 32));
+    const size_t row = ((size_t)row_hi << 32) | row_lo;  // the same in every lane of the wavefront: everything derived from it is scalar
+    const size_t t = row / (size_t)Hc;
+    const int oy = (int)(row - t * (size_t)Hc);
+    const int first = bounds ? bounds[2 * oy] : y0 + oy, count = bounds ? bounds[2 * oy + 1] : 1;
+    const int32_t* k = bounds ? coefs + (size_t)oy * ksize : nullptr;
+    const uint8_t* base = src + t * fstride + (size_t)first * rstride + (size_t)xoff * C;
+    for (int c = 0; c < C; ++c) {
+      const size_t plane = ((t * (size_t)C + c) * Hc + oy) * (size_t)Wc;  // index of out[t][c][oy][0]
+      const int a = (int)((phase + (unsigned)(plane & 3)) & 3), ng = (Wc + a + 3) >> 2;
+      const float* tab = s_lut + c * 256;
+      for (int g = lane; g < ng; g += 64) {
+        const int e0 = 4 * g - a;
+        int col[4], acc[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int e = e0 + q;
+          col[q] = (e < 0 ? 0 : (e >= Wc ? Wc - 1 : e)) * C + c;  // a clipped element recomputes its neighbour and is not stored
+          acc[q] = 1 << (RU_BITS - 1);
+        }
+        for (int j = 0; j < count; ++j) {
+          const uint8_t* r = base + (size_t)j * rstride;
+          const int kj = bounds ? k[j] : (1 << RU_BITS);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) acc[q] += (int)r[col[q]] * kj;
+        }
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          int b = acc[q] >> RU_BITS;
+          b = b < 0 ? 0 : (b > 255 ? 255 : b);
+          v[q] = tab[b];
+        }
+        float* dst = out + plane + e0;
+        if (e0 >= 0 && e0 + 4 <= Wc) {
+          *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (e0 + q >= 0 && e0 + q < Wc) dst[q] = v[q];
+        }
+      }
+    }
+  }
+}
+
 constexpr int RU_MAX_BLOCKS = 16384;  // 256 CUs x 8 blocks of 256 threads, a few rounds of them: the loops above stride over the rest
 
 void ru_launch(const uint8_t* in, uint8_t* out, size_t rows, int n_in, int n_out, size_t elem, const int32_t* bounds, const int32_t* coefs,
@@ -226,6 +291,67 @@ extern "C" int wf_resample_u8(const uint8_t* in, uint8_t* out, int T, int h, int
   }
   if (ypass) ru_launch(src, out, (size_t)T, h, H, (size_t)W * C, ybounds, ycoefs, yk, s);
   WF_LAUNCH_CHECK("wf_resample_u8");
+  return WF_OK;
+}
+
+extern "C" size_t wf_resample_u8_window_f32_workspace_bytes(int T, int h, int w, int H, int W, int C, int y0, int x0, int Hc, int Wc) {
+  if (T <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || Hc <= 0 || Wc <= 0 || (C != 1 && C != 3)) return 0;
+  if (y0 < 0 || x0 < 0 || (long long)y0 + Hc > H || (long long)x0 + Wc > W) return 0;
+  if (w == W) return 256;
+  return al256((size_t)T * h * Wc * C);  // the column pass's u8 rows [T][h][Wc][C], addressed by source row
+}
+
+extern "C" int wf_resample_u8_window_f32(const uint8_t* in, float* out, int T, int h, int w, int H, int W, int C, int y0, int x0, int Hc,
+                                         int Wc, const int32_t* xbounds, const int32_t* xcoefs, int xk, const int32_t* ybounds,
+                                         const int32_t* ycoefs, int yk, const float* lut, void* workspace, void* stream) {
+  WF_CHECK_ARG(T > 0 && h > 0 && w > 0 && H > 0 && W > 0 && Hc > 0 && Wc > 0, "wf_resample_u8_window_f32: empty problem");
+  WF_CHECK_ARG(C == 1 || C == 3, "wf_resample_u8_window_f32: C = %d, 1 or 3 only", C);
+  WF_CHECK_ARG(y0 >= 0 && x0 >= 0 && (long long)y0 + Hc <= H && (long long)x0 + Wc <= W,
+               "wf_resample_u8_window_f32: the window %d x %d at (%d, %d) leaves %d x %d", Hc, Wc, y0, x0, H, W);
+  WF_CHECK_ARG(in && out && lut, "wf_resample_u8_window_f32: null pointer");
+  WF_CHECK_ARG((size_t)W * C < ((size_t)1 << 31) && (size_t)w * C < ((size_t)1 << 31), "wf_resample_u8_window_f32: a row of 2^31 bytes or more");
+  const bool xpass = w != W, ypass = h != H;
+  WF_CHECK_ARG(!xpass || (xbounds && xcoefs && xk > 0), "wf_resample_u8_window_f32: the column pass needs its tables");
+  WF_CHECK_ARG(!ypass || (ybounds && ycoefs && yk > 0), "wf_resample_u8_window_f32: the row pass needs its tables");
+  WF_CHECK_ARG(!xpass || workspace, "wf_resample_u8_window_f32: the column pass needs the workspace");
+  hipStream_t s = (hipStream_t)stream;
+  const uint8_t* src = in;
+  size_t fstride = (size_t)h * w * C, rstride = (size_t)w * C;
+  int xoff = x0;
+  if (xpass) {
+    // Source rows the window's output rows can tap.  The tables live on the device, so the range is taken from the geometry they were
+    // built from: a tap window is centred at (i + 0.5) h / H and reaches (yk - 1) / 2 >= the support to either side; one row of slack each
+    // way covers the rounding.  A row outside the exact range costs time only; the intermediate is addressed by source row.
+    int r0 = 0, r1 = h;
+    if (ypass) {
+      const double scale = (double)h / (double)H, half = 0.5 * (yk - 1) + 0.5;
+      const double lo = floor((y0 + 0.5) * scale - half) - 1.0, hi = ceil((y0 + Hc - 0.5) * scale + half) + 1.0;
+      r0 = lo < 0.0 ? 0 : (int)lo;
+      r1 = hi > (double)h ? h : (int)hi;
+    } else {
+      r0 = y0;
+      r1 = y0 + Hc;
+    }
+    uint8_t* mid = (uint8_t*)workspace;
+    const size_t mrow = (size_t)Wc * C;
+    const int32_t* xb = xbounds + 2 * (size_t)x0;
+    const int32_t* xc = xcoefs + (size_t)x0 * xk;
+    if (r0 == 0 && r1 == h) {
+      ru_launch(in, mid, (size_t)T * h, w, Wc, (size_t)C, xb, xc, xk, s);
+    } else {
+      for (int t = 0; t < T; ++t)
+        ru_launch(in + ((size_t)t * h + r0) * rstride, mid + ((size_t)t * h + r0) * mrow, (size_t)(r1 - r0), w, Wc, (size_t)C, xb, xc, xk, s);
+    }
+    src = mid;
+    fstride = (size_t)h * mrow;
+    rstride = mrow;
+    xoff = 0;
+  }
+  const size_t rows = (size_t)T * Hc;
+  hipLaunchKernelGGL(k_ru_window_lut, dim3(grid_for((rows + 3) / 4 * 256, 256, RS_MAX_BLOCKS)), dim3(256), 0, s, src, fstride, rstride, xoff, y0,
+                     ypass ? ybounds + 2 * (size_t)y0 : (const int32_t*)nullptr, ypass ? ycoefs + (size_t)y0 * yk : (const int32_t*)nullptr, yk,
+                     lut, out, T, C, Hc, Wc);
+  WF_LAUNCH_CHECK("wf_resample_u8_window_f32");
   return WF_OK;
 }
 

@@ -14,7 +14,7 @@ loop consumes their outputs.  Those come in through --embeds (a .npz / .safetens
 `transformers` is importable, are computed with those classes exactly as PIPE:166-214 does (--text-encoder transformers --image-encoder
 transformers, the defaults).  --text-encoder native runs the UMT5 weights on this engine's own kernels instead (worldforge_amd/umt5.py) and
 --image-encoder native the CLIP vision weights, in float32 as the reference loads them (worldforge_amd/clip.py, with the image processor's PIL
-path restated on the host).  With both native, the only thing of `transformers` that is touched is the tokenizer (data plus a host library).
+path restated bit for bit on the device).  With both native, the only thing of `transformers` that is touched is the tokenizer (data plus a host library).
 The reference's scene -> prompt table (utils/prompts.py) is text data of the reference and is not shipped: pass --prompt; the negative
 prompt defaults to the entry point's own two literals (INFER:277-285, by --static).
 """
@@ -110,8 +110,10 @@ def run(models_dir: Optional[str], video_ref: str, model: str = "720p", output: 
     as keywords under the stage-1 commands' own names (vggt_checkpoint, image_path, direction, ... / video_path, depth_npz, ...; see
     stage1.py), and its frames reach the sampler through harness.prepare_inputs_device without leaving the device; save_stage1 also writes
     them as PNG files.  stage1_frames = (images u8 [F,H,W,3], masks u8 [F,H,W] 0 / 1) hands over tensors a caller already holds.  The
-    tensors are bit-identical to the file route's.  Stated deviation: the in-process route keeps stage 1's frame order; the file route
-    sorts the file names, which is the same order for fewer than 100 frames and label angles below 100 degrees."""
+    tensors are bit-identical to the file route's.  With image_encoder="native" and no `image`, clip.encode_image is handed the first
+    frame at the sampler's size as a device tensor (the PIL image's bits) and preprocesses it there.  Stated deviation: the in-process
+    route keeps stage 1's frame order; the file route sorts the file names, which is the same order for fewer than 100 frames and label
+    angles below 100 degrees."""
     from . import stage1 as stage1_mod
     from .dit import WanTransformer3DModel
     from .pipeline import WanImageToVideoPipeline
@@ -155,8 +157,13 @@ def run(models_dir: Optional[str], video_ref: str, model: str = "720p", output: 
     # raises (scheduling_unipc_multistep_clean.py:1326), so a mismatch is an error here too, before any GPU work.
     prep = dict(model=model, num_frames=None, soften=soften_mask, transition_distance=transition_distance, decay_type=decay_type, device=dev,
                 max_area=max_area, image=image)
+    clip_image = None
     if in_process:
         pil, video, mask, height, width = harness.prepare_inputs_device(images_u8, masks_u8, **prep)
+        if image_encoder == "native" and image is None and embeds is None:
+            # the native image encoder takes the frame where it is: `pil` is images_u8[0] resized to (height, width), and so is this
+            from . import ops
+            clip_image = ops.resample_u8(images_u8[:1].contiguous(), (height, width))[0]
         del images_u8, masks_u8
     else:
         pil, video, mask, height, width = harness.prepare_inputs(video_ref, **prep)
@@ -170,7 +177,8 @@ def run(models_dir: Optional[str], video_ref: str, model: str = "720p", output: 
     elif model_path is not None and all(os.path.isdir(os.path.join(model_path, d)) for d in ("text_encoder", "tokenizer", "image_encoder", "image_processor")):
         if prompt is None:
             raise ValueError("pass --prompt (the reference's scene -> prompt table utils/prompts.py is not shipped)")
-        emb = encode_with_transformers(model_path, prompt, negative_prompt, pil, dev, text_encoder=text_encoder, image_encoder=image_encoder)
+        emb = encode_with_transformers(model_path, prompt, negative_prompt, pil if clip_image is None else clip_image, dev,
+                                       text_encoder=text_encoder, image_encoder=image_encoder)
     else:
         raise ValueError("no --embeds file and no text_encoder / image_encoder folders to compute them from")
 

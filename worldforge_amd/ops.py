@@ -257,12 +257,13 @@ def soften_mask(mask: torch.Tensor, transition_distance: int = 15, decay_type: s
 _RESAMPLE_TABLES: dict = {}
 
 
-def _resample_tables(n_in: int, n_out: int, device):
-    """Pillow's tables of one axis on `device` (bounds, coefs, ksize), built and checked once per (in, out, device): they are read-only."""
+def _resample_tables(n_in: int, n_out: int, device, filter: str = "bicubic"):
+    """Pillow's tables of one axis on `device` (bounds, coefs, ksize), built and checked once per (in, out, filter, device): they are
+    read-only."""
     from . import resample
-    key = (n_in, n_out, str(device))
+    key = (n_in, n_out, filter, str(device))
     if key not in _RESAMPLE_TABLES:
-        bounds, coefs = resample.pil_resample_tables(n_in, n_out)
+        bounds, coefs = resample.filter_tables(n_in, n_out, filter)
         if bounds[:, 0].min() < 0 or bounds[:, 1].min() < 1 or (bounds[:, 0] + bounds[:, 1]).max() > n_in or bounds[:, 1].max() > coefs.shape[1]:
             raise ValueError(f"resample tables {n_in} -> {n_out}: a tap window leaves the axis")   # the C entry trusts what it is handed
         if len(_RESAMPLE_TABLES) >= 64:
@@ -271,11 +272,22 @@ def _resample_tables(n_in: int, n_out: int, device):
     return _RESAMPLE_TABLES[key]
 
 
-def resample_u8(frames: torch.Tensor, size_hw) -> torch.Tensor:
-    """`PIL.Image.resize((W, H))` (bicubic, Pillow's default for modes RGB and L) of every frame, bit for bit, on the device
-    (wf_resample_u8): frames u8 [T, h, w, C] (C = 1 or 3) or [T, h, w] -> u8 of the same rank at H x W.  Pillow's coefficient tables
-    are built here on the host (resample.pil_resample_tables; kept per size pair) and uploaded, so the kernel only ever reads tables whose taps lie inside
-    the image."""
+def _axis_tables(frames_hw, size_hw, device, filter: str):
+    """[xbounds, xcoefs, xk, ybounds, ycoefs, yk] for the C entries: columns first, None / 0 for an axis whose size does not change."""
+    from . import resample
+    if filter not in resample.FILTERS:
+        raise ValueError(f"filter {filter!r}: one of {sorted(resample.FILTERS)}")
+    tabs = []
+    for n_in, n_out in ((frames_hw[1], size_hw[1]), (frames_hw[0], size_hw[0])):
+        tabs += [None, None, 0] if n_in == n_out else list(_resample_tables(n_in, n_out, device, filter))
+    return tabs
+
+
+def resample_u8(frames: torch.Tensor, size_hw, filter: str = "bicubic") -> torch.Tensor:
+    """`PIL.Image.resize((W, H), filter)` (bicubic: Pillow's default for modes RGB and L) of every frame, bit for bit, on the device
+    (wf_resample_u8): frames u8 [T, h, w, C] (C = 1 or 3) or [T, h, w] -> u8 of the same rank at H x W.  `filter`: one of Pillow's five
+    convolution filters (resample.FILTERS).  Pillow's coefficient tables are built here on the host (resample.filter_tables; kept per
+    size pair and filter) and uploaded, so the kernel only ever reads tables whose taps lie inside the image."""
     frames = _dev(frames)
     if frames.dtype != torch.uint8 or frames.dim() not in (3, 4):
         raise TypeError(f"resample_u8: uint8 [T, h, w, C] or [T, h, w], got {frames.dtype} {tuple(frames.shape)}")
@@ -286,17 +298,39 @@ def resample_u8(frames: torch.Tensor, size_hw) -> torch.Tensor:
     if C not in (1, 3) or min(T, h, w, H, W) <= 0:
         raise ValueError(f"resample_u8: {tuple(frames.shape)} -> {(H, W)}: sizes must be positive and C 1 or 3")
     dev = frames.device
-    tabs = []
-    for n_in, n_out in ((w, W), (h, H)):
-        if n_in == n_out:
-            tabs += [None, None, 0]
-            continue
-        tabs += list(_resample_tables(n_in, n_out, dev))
+    tabs = _axis_tables((h, w), (H, W), dev, filter)
     out = torch.empty((T, H, W) if planar else (T, H, W, C), dtype=torch.uint8, device=dev)
     ws = torch.empty(int(_ffi.lib().wf_resample_u8_workspace_bytes(T, h, w, H, W, C)), dtype=torch.uint8, device=dev)
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     call("wf_resample_u8", frames.data_ptr(), out.data_ptr(), T, h, w, H, W, C, ptr(tabs[0]), ptr(tabs[1]), tabs[2], ptr(tabs[3]),
          ptr(tabs[4]), tabs[5], ws.data_ptr(), stream())
+    return out
+
+
+def resample_u8_window(frames: torch.Tensor, size_hw, window, lut: torch.Tensor, filter: str = "bicubic") -> torch.Tensor:
+    """A network's fp32 input from decoded pixels in one entry (wf_resample_u8_window_f32): frames u8 [T, h, w, C] (C = 1 or 3) or
+    [T, h, w] -> f32 [T, C, Hc, Wc] = lut[c][resample_u8(frames, size_hw, filter)[:, y0:y0 + Hc, x0:x0 + Wc, c]], window = (y0, x0, Hc, Wc),
+    lut f32 [C, 256] (or [256] for C = 1): the host's own u8 -> f32 expression per channel.  Only the window is computed."""
+    frames, lut = _dev(frames), _dev(lut)
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4):
+        raise TypeError(f"resample_u8_window: uint8 [T, h, w, C] or [T, h, w], got {frames.dtype} {tuple(frames.shape)}")
+    T, h, w = frames.shape[:3]
+    C = 1 if frames.dim() == 3 else frames.shape[3]
+    H, W = int(size_hw[0]), int(size_hw[1])
+    y0, x0, Hc, Wc = (int(v) for v in window)
+    if C not in (1, 3) or min(T, h, w, H, W, Hc, Wc) <= 0:
+        raise ValueError(f"resample_u8_window: {tuple(frames.shape)} -> {(H, W)}, window {(y0, x0, Hc, Wc)}: sizes must be positive and C 1 or 3")
+    if y0 < 0 or x0 < 0 or y0 + Hc > H or x0 + Wc > W:
+        raise ValueError(f"resample_u8_window: the window {Hc} x {Wc} at {(y0, x0)} leaves {H} x {W}")
+    if lut.dtype != torch.float32 or lut.numel() != C * 256:
+        raise TypeError(f"resample_u8_window: a float32 table [{C}, 256], got {lut.dtype} {tuple(lut.shape)}")
+    dev = frames.device
+    tabs = _axis_tables((h, w), (H, W), dev, filter)
+    out = torch.empty((T, C, Hc, Wc), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(_ffi.lib().wf_resample_u8_window_f32_workspace_bytes(T, h, w, H, W, C, y0, x0, Hc, Wc)), dtype=torch.uint8, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    call("wf_resample_u8_window_f32", frames.data_ptr(), out.data_ptr(), T, h, w, H, W, C, y0, x0, Hc, Wc, ptr(tabs[0]), ptr(tabs[1]), tabs[2],
+         ptr(tabs[3]), ptr(tabs[4]), tabs[5], lut.data_ptr(), ws.data_ptr(), stream())
     return out
 
 

@@ -130,7 +130,7 @@ def warp_frames(args, device=None):
     if args.camera >= len(names):
         print(f"Warning: camera index {args.camera} out of range, using 0")
         args.camera = 0
-    x = vggt.preprocess([Image.open(p) for p in names])
+    x = vggt.preprocess_device([Image.open(p) for p in names], device)
     print("Running model inference...")
     r = model.predict(x)
     idx = args.camera

@@ -352,6 +352,55 @@ def preprocess(pil_images: Sequence, mode: str = "crop", target: int = 518) -> t
     return torch.stack(out)
 
 
+def preprocess_device(images: Sequence, device, mode: str = "crop", target: int = 518) -> torch.Tensor:
+    """preprocess on the device, bit for bit: PIL images or u8 [h, w, 3] arrays / tensors (host or device) -> fp32 [N, 3, H, W] on
+    `device`.  On the host stays what decoding does there (RGBA over white, convert("RGB")); the bicubic resize, the centre crop, u8 ->
+    f32 and the move to planar are one entry (ops.resample_u8_window) that computes the cropped rows only, images of equal source size in
+    one call.  The 256-entry table is preprocess' own expression on every byte value.  The same refusals as preprocess."""
+    from PIL import Image
+
+    from . import ops
+    if len(images) == 0:
+        raise ValueError("At least 1 image is required")
+    if mode == "pad":
+        raise NotImplementedError('mode="pad" is not implemented')
+    if mode != "crop":
+        raise ValueError("Mode must be either 'crop' or 'pad'")
+    px = []
+    for img in images:
+        if isinstance(img, Image.Image):
+            if img.mode == "RGBA":
+                img = Image.alpha_composite(Image.new("RGBA", img.size, (255, 255, 255, 255)), img)
+            img = torch.from_numpy(np.asarray(img.convert("RGB")).copy())
+        elif isinstance(img, np.ndarray):
+            img = torch.from_numpy(img)
+        if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+            raise TypeError(f"preprocess_device takes PIL images or uint8 [h, w, 3] arrays / tensors, got {type(img)}")
+        px.append(img)
+    plans = []
+    for x in px:
+        h, w = x.shape[:2]
+        nh = round(h * (target / w) / 14) * 14
+        plans.append((nh, (nh - target) // 2 if nh > target else 0, min(nh, target)))
+    if len({p[2] for p in plans}) > 1:
+        raise NotImplementedError(f"images of mixed shapes {sorted({(p[2], target) for p in plans})} are not implemented")
+    lut = torch.tensor(np.arange(256, dtype=np.uint8)).float().div(255).expand(3, 256).contiguous().to(device)
+    groups: Dict[Tuple[int, int], list] = {}
+    for i, x in enumerate(px):
+        groups.setdefault(tuple(x.shape[:2]), []).append(i)
+    out = None
+    for idx in groups.values():
+        nh, y0, Hc = plans[idx[0]]
+        frames = torch.stack([px[i].to(device) for i in idx])
+        x = ops.resample_u8_window(frames, (nh, target), (y0, 0, Hc, target), lut)
+        if len(groups) == 1:
+            return x
+        if out is None:
+            out = torch.empty((len(px),) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+        out[idx] = x
+    return out
+
+
 class VGGT:
     def __init__(self, cfg: Optional[VGGTConfig] = None, device="cuda:0"):
         self.cfg = cfg or VGGTConfig()
@@ -829,7 +878,7 @@ def main(argv=None) -> int:
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--depth", action="store_true", help="load the DPT depth head too and add depth [1, S, H, W, 1], depth_conf [1, S, H, W] to the npz")
     a = ap.parse_args(argv)
-    x = preprocess([Image.open(p) for p in a.images])
+    x = preprocess_device([Image.open(p) for p in a.images], a.device)
     model = VGGT.from_pretrained(a.checkpoint, device=a.device, depth=a.depth)
     extra = {}
     if a.depth:
